@@ -4,9 +4,13 @@ single-GPU leg of that config).
 
 Contract: `python bench.py --gpus N --steps K --warmup W` (N>1 launched by
 the driver via torch.distributed.run, one rank per GPU over RCCL). Rank 0
-prints ONE JSON line with the whole-node throughput, the roofline of the
-dominant hand-written kernel (measured live with HIP events), and the oracle
-CPU baseline (kind "port") timed on the host cores.
+prints ONE JSON line with the whole-node throughput and the roofline of the
+dominant hand-written kernel (measured live with HIP events inside the timed
+steps). `--full` adds the oracle CPU baseline (kind "port") timed on the
+host cores, which takes minutes; a plain run leaves `cpu_baseline` null.
+`--dump-outputs DIR` writes what the last timed step computed (see
+dump_outputs) so two builds can be compared output for output: with the
+same arguments the initial weights and every batch are identical.
 
 A "step" = one train_step: padding-free forward + backward + ZeRO-2
 reduce-scatter/AdamW/all-gather on synthetic packed seq-4096 batches
@@ -170,8 +174,46 @@ def run_steps(wrapper, engine, scheduler, rank, mbs, seq_len, vocab, n_steps, st
             return b
 
     it = _It()
+    results = []
     for _ in range(n_steps):
-        train_step(wrapper, engine, scheduler, it, 1, clip)
+        results.append(train_step(wrapper, engine, scheduler, it, 1, clip))
+    return results
+
+
+DUMP_SAMPLE_PER_BUCKET = 65536  # elements sampled from each optimizer bucket
+DUMP_SEED = 20240229
+WEIGHT_SEED = 1234  # torch seed set before the model is built
+
+
+def dump_outputs(out_dir, step_results, engine):
+    """Write what the last timed train_step handed back to its caller, as
+    float64/float32 .npy files: the (loss, grad_norm) it returned, the loss
+    of every timed step, and the parameters it left behind. The parameters
+    are read from the optimizer's fp32 master shards, not from the bf16
+    model copies: at lr 1e-5 a few AdamW steps move almost no bf16 value,
+    while every master value moves. They are a fixed seeded sample
+    (DUMP_SAMPLE_PER_BUCKET elements per bucket of this rank's shard, same
+    indices every run) so the dump stays far below 64 MB at 3B/8B."""
+    import numpy
+
+    os.makedirs(out_dir, exist_ok=True)
+    last_loss, last_grad_norm = step_results[-1]
+    numpy.save(os.path.join(out_dir, "loss.npy"), numpy.array([last_loss], dtype=numpy.float64))
+    numpy.save(os.path.join(out_dir, "grad_norm.npy"), numpy.array([last_grad_norm], dtype=numpy.float64))
+    numpy.save(
+        os.path.join(out_dir, "loss_per_step.npy"),
+        numpy.array([r[0] for r in step_results], dtype=numpy.float64),
+    )
+
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    chunks = []
+    for b in engine.buckets:
+        flat = b.master.detach()
+        if flat.numel() > DUMP_SAMPLE_PER_BUCKET:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE_PER_BUCKET,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        chunks.append(flat.float().cpu())
+    numpy.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(chunks).numpy())
 
 
 def cpu_baseline(args):
@@ -281,7 +323,13 @@ def main():
     ap.add_argument("--model", choices=sorted(MODELS), default="3b",
                     help="3b = BASELINE config #3 (the headline metric); 350m = config #2")
     ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the oracle CPU baseline (minutes of host time); a plain run "
+                         "only sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
     if args.seq_len is None:
         args.seq_len = {"350m": 2048, "llama8b": 8192}.get(args.model, SEQ_LEN)
     if args.micro_batch is None:
@@ -301,6 +349,8 @@ def main():
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
     torch.cuda.set_device(device)
 
+    # same arguments -> same initial weights (the batches are seeded per step)
+    torch.manual_seed(WEIGHT_SEED)
     wrapper, engine = build(args, device)
     scheduler = LRScheduler(1e-5, 0, 0, None, 10**9, "constant", 0.1)
     vocab = MODELS[args.model]["vocab_size"]
@@ -314,7 +364,7 @@ def main():
     # timed region (per-op HIP events enabled for the roofline evidence)
     hip.enable_profiling()
     t0 = time.perf_counter()
-    run_steps(
+    step_results = run_steps(
         wrapper, engine, scheduler, rank, args.micro_batch, args.seq_len, vocab, args.steps, step0=args.warmup
     )
     if world > 1:
@@ -331,6 +381,9 @@ def main():
 
     if rank != 0:
         return
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_results, engine)
 
     tokens_total = args.micro_batch * args.seq_len * args.steps * world
     value = tokens_total / elapsed
@@ -412,7 +465,7 @@ def main():
         }
 
     cpu = None
-    if not args.skip_cpu_baseline and world == 1 and args.model == "3b":
+    if args.full and not args.skip_cpu_baseline and world == 1 and args.model == "3b":
         cpu = cpu_baseline(args)
 
     result = {

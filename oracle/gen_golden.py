@@ -13,6 +13,9 @@ it, the HIP product path) to the reference's own CPU eager path:
     model_wrapper/pretraining.py:125, optimization/optimizer.py:74).
   - scheduler.pt    : lr factors from the reference scheduler closures
     (optimization/scheduler.py) at sampled steps.
+  - fim_permute.npz, yarn_rope.npz, model_alibi_mqa.pt : recorded
+    outputs of the reference's FIM permute, YaRN rope tables and alibi model
+    (`python -m oracle.gen_golden extras` writes only these).
 
 The committed fixtures + this script are the parity anchor.
 """
@@ -23,6 +26,8 @@ import types
 from pathlib import Path
 
 import torch
+
+from oracle.golden import save_golden
 
 GOLDEN_DIR = Path(__file__).resolve().parent.parent / "tests" / "golden"
 
@@ -109,7 +114,7 @@ def gen_model_cases():
         out.loss.backward()
         grads = {k: dict(model.named_parameters())[k].grad.detach().clone() for k in GRAD_KEYS if k in dict(model.named_parameters())}
 
-        torch.save(
+        save_golden(
             dict(
                 config=cfg_kwargs,
                 state_dict={k: v.detach().clone() for k, v in model.state_dict().items()},
@@ -172,7 +177,7 @@ def gen_moe_case():
     out.loss.backward()
     grads_with_aux = {k: params[k].grad.detach().clone() for k in MOE_GRAD_KEYS if k in params}
 
-    torch.save(
+    save_golden(
         dict(
             config=cfg_kwargs,
             state_dict={k: v.detach().clone() for k, v in model.state_dict().items()},
@@ -316,14 +321,126 @@ def gen_scheduler():
     print("scheduler.pt written")
 
 
+FIM_SEEDS = range(6)
+FIM_RATES = ((1.0, 0.0), (1.0, 1.0), (0.5, 0.5), (0.0, 0.5))  # (fim_rate, fim_spm_rate)
+
+
+def gen_fim_permute():
+    """fim_permute.npz: outputs of the reference's permute
+    (gpt_dataset.py:513-600) on a fixed sample, per RandomState seed and
+    (rate, spm rate), with the test suite's identity tokenizer."""
+    import re
+
+    import numpy
+
+    from oracle.ref_shim import REFERENCE_PATH
+    from tests.test_megatron_data import _FakeFimTokenizer
+
+    # gpt_dataset imports heavy siblings; run just the permute function
+    src = open(f"{REFERENCE_PATH}/dolomite_engine/data/megatron/gpt_dataset.py").read()
+    start = src.find("def permute(")
+    assert start > 0
+    m = re.search(r"\ndef \w+\(", src[start + 10 :])
+    fn_src = src[start : start + 10 + m.start()] if m else src[start:]
+    ns = {"numpy": numpy, "AutoTokenizer": object}  # annotation-only name
+    exec(fn_src, ns)
+    ref_permute = ns["permute"]
+
+    tok = _FakeFimTokenizer()
+    out = {}
+    for seed in FIM_SEEDS:
+        for i, (rate, spm) in enumerate(FIM_RATES):
+            sample = numpy.arange(10, 30, dtype=numpy.int64)
+            theirs, _ = ref_permute(sample.copy(), numpy.random.RandomState(seed), rate, spm, tok,
+                                    truncate_or_pad=False, suffix_tok_id=9001, prefix_tok_id=9002,
+                                    middle_tok_id=9003, pad_tok_id=9004)
+            out[f"seed{seed}_case{i}"] = numpy.asarray(theirs, dtype=numpy.int64)
+    numpy.savez(GOLDEN_DIR / "fim_permute.npz", **out)
+    print("fim_permute.npz written:", len(out), "cases")
+
+
+YARN_CASES = [(64, 4.0, 2048), (128, 8.0, 4096), (80, 2.0, 1024), (64, 1.0, 2048)]  # (head_dim, scale, orig)
+
+
+def gen_yarn_rope():
+    """yarn_rope.npz: cos/sin tables of the reference YaRNScaledRoPE
+    (position_embedding/rope.py:59-142), first 512 positions, per case."""
+    import numpy
+
+    from oracle.ref_shim import REFERENCE_PATH
+
+    sys.path.insert(0, REFERENCE_PATH)
+    try:
+        spec = importlib.util.spec_from_file_location(
+            "_ref_rope", f"{REFERENCE_PATH}/dolomite_engine/hf_models/modeling_utils/position_embedding/rope.py"
+        )
+        ref_rope = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(ref_rope)
+    finally:
+        sys.path.remove(REFERENCE_PATH)
+
+    out = {}
+    for i, (head_dim, scale, orig) in enumerate(YARN_CASES):
+        ref = ref_rope.YaRNScaledRoPE(
+            head_dim, max_position_embeddings=512, base=10000, scale=scale,
+            original_max_position_embeddings=orig,
+        )
+        out[f"case{i}_params"] = numpy.array([head_dim, scale, orig], dtype=numpy.float64)
+        out[f"case{i}_cos"] = ref.cos_cached[:512].numpy()
+        out[f"case{i}_sin"] = ref.sin_cached[:512].numpy()
+    numpy.savez_compressed(GOLDEN_DIR / "yarn_rope.npz", **out)
+    print("yarn_rope.npz written")
+
+
+ALIBI_CONFIG = dict(
+    vocab_size=160, n_positions=64, n_embd=48, n_layer=2, n_head=6,
+    attention_head_type="mqa", n_inner=96, activation_function="gelu_pytorch_tanh",
+    normalization_function="rmsnorm", position_embedding_type="alibi",
+    resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0, tie_word_embeddings=False,
+)
+
+
+def gen_alibi():
+    """model_alibi_mqa.pt: the reference model with alibi positions run
+    directly (base.py:261-287, alibi.py slopes), eager and sdpa, with and
+    without a left-padded attention mask."""
+    from oracle.ref_shim import make_reference_config, make_reference_model
+
+    g = torch.Generator().manual_seed(5)
+    ids = torch.randint(0, 160, (2, 33), generator=g)
+    mask = torch.ones(2, 33, dtype=torch.long)
+    mask[1, :7] = 0  # left padding on row 1
+
+    fx = dict(config=dict(ALIBI_CONFIG), input_ids=ids, attention_mask=mask)
+    for impl in ("eager", "sdpa"):
+        torch.manual_seed(11)
+        rmodel = make_reference_model(make_reference_config(**ALIBI_CONFIG), attn_implementation=impl)
+        rmodel.eval()
+        with torch.no_grad():
+            fx[impl] = dict(
+                state_dict={k: v.detach().clone() for k, v in rmodel.state_dict().items()},
+                logits=rmodel(input_ids=ids).logits.clone(),
+                logits_masked=rmodel(input_ids=ids, attention_mask=mask).logits.clone(),
+            )
+    torch.save(fx, GOLDEN_DIR / "model_alibi_mqa.pt")
+    print("model_alibi_mqa.pt written")
+
+
 if __name__ == "__main__":
     GOLDEN_DIR.mkdir(parents=True, exist_ok=True)
     import sys as _sys
 
     if len(_sys.argv) > 1 and _sys.argv[1] == "moe":
         gen_moe_case()
+    elif len(_sys.argv) > 1 and _sys.argv[1] == "extras":
+        gen_fim_permute()
+        gen_yarn_rope()
+        gen_alibi()
     else:
         gen_model_cases()
         gen_moe_case()
         gen_ops()
         gen_scheduler()
+        gen_fim_permute()
+        gen_yarn_rope()
+        gen_alibi()

@@ -458,7 +458,9 @@ class TestMoEGroupedGemm:
         p = golden_dir / FIXTURE
         if not p.exists():
             pytest.skip("moe golden missing")
-        fx = torch.load(p, weights_only=False)
+        from oracle.golden import load_golden
+
+        fx = load_golden(p)
         model = build_moe(fx, "flash_attention_2", padding_free=True, dtype=torch.bfloat16).cuda()
         B, S = fx["input_ids"].shape
         hip_mod.enable_profiling()

@@ -37,7 +37,9 @@ def _load(golden_dir, name):
     p = golden_dir / name
     if not p.exists():
         pytest.skip(f"golden fixture {name} missing")
-    return torch.load(p, weights_only=False)
+    from oracle.golden import load_golden
+
+    return load_golden(p)
 
 
 def _oracle_from_fixture(fx):

@@ -25,7 +25,9 @@ def _load(golden_dir, name):
     p = golden_dir / name
     if not p.exists():
         pytest.skip(f"golden fixture {name} missing")
-    return torch.load(p, weights_only=False)
+    from oracle.golden import load_golden
+
+    return load_golden(p)
 
 
 def build_model(fx, attn_implementation="eager", padding_free=False, dtype=torch.float32):
@@ -169,36 +171,21 @@ def test_gradient_checkpointing_matches_plain(golden_dir):
         torch.testing.assert_close(grads_a[k], grads_b[k], rtol=1e-6, atol=1e-7, msg=lambda m: f"{k}: {m}")
 
 
-import os as _os
-
-
-@pytest.mark.skipif(not _os.path.isdir("/root/reference"), reason="reference checkout not present")
-def test_yarn_rope_tables_match_reference():
-    """YaRNScaledRoPE cos/sin tables bit-match the reference implementation
-    (position_embedding/rope.py:59-142) over scales and head dims."""
-    import importlib.util
-    import sys
-
-    sys.path.insert(0, "/root/reference")
-    try:
-        spec = importlib.util.spec_from_file_location(
-            "_ref_rope", "/root/reference/dolomite_engine/hf_models/modeling_utils/position_embedding/rope.py"
-        )
-        ref_rope = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref_rope)
-    finally:
-        sys.path.remove("/root/reference")
+def test_yarn_rope_tables_match_reference(golden_dir):
+    """YaRNScaledRoPE cos/sin tables bit-match the recorded tables of the
+    reference implementation (position_embedding/rope.py:59-142;
+    oracle/gen_golden.py gen_yarn_rope) over scales and head dims."""
+    import numpy
 
     from dolomite_engine_amd.hf_models.modeling import YaRNScaledRoPE
 
-    for head_dim, scale, orig in [(64, 4.0, 2048), (128, 8.0, 4096), (80, 2.0, 1024), (64, 1.0, 2048)]:
+    ref = numpy.load(golden_dir / "yarn_rope.npz")
+    for i, (head_dim, scale, orig) in enumerate([(64, 4.0, 2048), (128, 8.0, 4096), (80, 2.0, 1024), (64, 1.0, 2048)]):
+        assert ref[f"case{i}_params"].tolist() == [head_dim, scale, orig]
+        assert ref[f"case{i}_cos"].shape == (512, head_dim)
         ours = YaRNScaledRoPE(head_dim, 512, 10000.0, scale=scale, original_max_position_embeddings=orig)
-        ref = ref_rope.YaRNScaledRoPE(
-            head_dim, max_position_embeddings=512, base=10000, scale=scale,
-            original_max_position_embeddings=orig,
-        )
-        torch.testing.assert_close(ours.cos_cached, ref.cos_cached[:512], rtol=0, atol=0)
-        torch.testing.assert_close(ours.sin_cached, ref.sin_cached[:512], rtol=0, atol=0)
+        torch.testing.assert_close(ours.cos_cached, torch.from_numpy(ref[f"case{i}_cos"]), rtol=0, atol=0)
+        torch.testing.assert_close(ours.sin_cached, torch.from_numpy(ref[f"case{i}_sin"]), rtol=0, atol=0)
 
 
 def test_yarn_model_forward_runs():
@@ -224,40 +211,30 @@ def test_yarn_model_forward_runs():
     assert torch.isfinite(out.loss)
 
 
-@pytest.mark.skipif(not _os.path.isdir("/root/reference"), reason="reference checkout not present")
 @pytest.mark.parametrize("impl", ["eager", "sdpa"])
-def test_alibi_dense_matches_reference(impl):
-    """position_embedding_type=alibi on the dense paths vs the reference
-    model run directly (base.py:261-287, alibi.py slopes)."""
-    from oracle.ref_shim import make_reference_config, make_reference_model
-
-    kw = dict(
-        vocab_size=160, n_positions=64, n_embd=48, n_layer=2, n_head=6,
-        attention_head_type="mqa", n_inner=96, activation_function="gelu_pytorch_tanh",
-        normalization_function="rmsnorm", position_embedding_type="alibi",
-        resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0, tie_word_embeddings=False,
-    )
-    torch.manual_seed(11)
-    rcfg = make_reference_config(**kw)
-    rmodel = make_reference_model(rcfg, attn_implementation=impl)
-    rmodel.eval()
+def test_alibi_dense_matches_reference(golden_dir, impl):
+    """position_embedding_type=alibi on the dense paths vs the recorded
+    logits of the reference model run directly (base.py:261-287, alibi.py
+    slopes; oracle/gen_golden.py gen_alibi), same weights and inputs."""
+    fx = torch.load(golden_dir / "model_alibi_mqa.pt", weights_only=False)
+    kw = fx["config"]
+    assert kw["position_embedding_type"] == "alibi"
 
     from dolomite_engine_amd.hf_models import GPTDolomiteConfig, GPTDolomiteForCausalLM
 
     cfg = GPTDolomiteConfig(**kw)
     cfg._attn_implementation = impl
     model = GPTDolomiteForCausalLM(cfg)
-    model.load_state_dict(rmodel.state_dict())
+    model.load_state_dict(fx[impl]["state_dict"])
     model.eval()
 
-    g = torch.Generator().manual_seed(5)
-    ids = torch.randint(0, 160, (2, 33), generator=g)
-    mask = torch.ones(2, 33, dtype=torch.long)
-    mask[1, :7] = 0  # left padding on row 1
+    ids = fx["input_ids"]
+    mask = fx["attention_mask"]
+    assert ids.shape == (2, 33) and int(mask[1, :7].sum()) == 0 and int(mask.sum()) == 2 * 33 - 7
+    ref_full = fx[impl]["logits"]
+    ref_mask = fx[impl]["logits_masked"]
     with torch.no_grad():
-        ref_full = rmodel(input_ids=ids).logits
         our_full = model(input_ids=ids).logits
-        ref_mask = rmodel(input_ids=ids, attention_mask=mask).logits
         our_mask = model(input_ids=ids, attention_mask=mask).logits
     torch.testing.assert_close(our_full, ref_full, rtol=1e-4, atol=1e-5)
     valid = mask.bool()

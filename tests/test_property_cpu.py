@@ -10,6 +10,7 @@ randomized shapes/contents beyond the fixed golden cases.
 """
 
 import numpy
+import pytest
 import torch
 from hypothesis import given, settings
 from hypothesis import strategies as st
@@ -74,6 +75,12 @@ def test_build_sample_idx_property(doc_lens, seq_length, num_epochs):
     sizes = numpy.array(doc_lens, dtype=numpy.int32)
     doc_idx = numpy.tile(numpy.arange(len(sizes), dtype=numpy.int32), num_epochs)
     tokens_per_epoch = int(sizes.sum())
+    if tokens_per_epoch <= 1:
+        # outside the builder's domain (helpers.cpp asserts tokens_per_epoch
+        # > 1): the native builder must refuse, not index past the stream
+        with pytest.raises(RuntimeError):
+            build_sample_idx(sizes, doc_idx, seq_length, num_epochs, tokens_per_epoch)
+        return
     if (num_epochs * tokens_per_epoch - 1) // seq_length <= 0:
         return
     got = build_sample_idx(sizes, doc_idx, seq_length, num_epochs, tokens_per_epoch)
