@@ -22,7 +22,13 @@
 //     atomics) reduced in fixed order by the finalize kernel —
 //     deterministic gradients; dq accumulates dQ in registers and stores
 //     bf16 straight into the packed dqkv.
-//   - dropout unsupported (hot-path configs run attn_pdrop = 0).
+//   - attention dropout (flash_attn_varlen_func's dropout_p) is fused: the
+//     keep-mask is a pure counter-based hash of (seed, q-head, global q
+//     token, global k token) — see "Attention dropout keep-mask" below and
+//     include/dolomite_hip.h — regenerated identically by fwd, dkv and dq
+//     from their own lane->(q, k) mappings and never written to memory.
+//     The kernels are templated on DROPOUT; p = 0 dispatches the
+//     DROPOUT=false instantiations, which compile to the dropout-free code.
 //
 // Fragment layout assumption for mfma_f32_16x16x32_bf16 (verified on
 // hardware by dolomite_mfma_probe, tests/test_gpu_kernels.py):
@@ -215,16 +221,74 @@ __device__ __forceinline__ void xcd_remap_tile_bh(int& tile, int& b, int& h) {
 }
 
 // ===========================================================================
+// Attention dropout keep-mask (definition: include/dolomite_hip.h; Python
+// restatement: ops/functional.py attention_dropout_keep_mask).
+//
+// keep(seed, h, t_q, t_k) is a pure function of the 64-bit seed, the q-head
+// and the GLOBAL packed token indices, so fwd, dkv and dq — which hold P in
+// three different lane layouts — regenerate the same bit without ever
+// storing the mask. Per element and integer-only: the per-row word depends
+// on (seed_lo, t_q), the per-column word on (seed_hi, h, t_k); whichever of
+// the two is fixed for a lane is hoisted out of the tile loop, the other is
+// computed once per 4 elements, and only drop_keep_words runs per element.
+// ===========================================================================
+#define DOL_DROP_CQ 0x9E3779B1u
+#define DOL_DROP_CK 0x85EBCA77u
+#define DOL_DROP_CH 0xC2B2AE3Du
+#define DOL_DROP_M1 0x7FEB352Du
+#define DOL_DROP_M2 0x846CA68Bu
+
+__device__ __forceinline__ uint32_t drop_mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= DOL_DROP_M1;
+    x ^= x >> 15;
+    x *= DOL_DROP_M2;
+    x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ uint32_t drop_head_word(uint32_t seed_hi, uint32_t h) {
+    return drop_mix32(seed_hi ^ (h * DOL_DROP_CH));
+}
+__device__ __forceinline__ uint32_t drop_row_word(uint32_t seed_lo, uint32_t t_q) {
+    return drop_mix32(seed_lo ^ (t_q * DOL_DROP_CQ));
+}
+__device__ __forceinline__ uint32_t drop_col_word(uint32_t head_word, uint32_t t_k) {
+    return drop_mix32(head_word ^ (t_k * DOL_DROP_CK));
+}
+// the compare reads x from the top, so the mixer's last xorshift (which only
+// folds high bits into the low half) is omitted
+__device__ __forceinline__ bool drop_keep_words(uint32_t rw, uint32_t cw, uint32_t thr) {
+    uint32_t x = rw ^ cw;
+    x ^= x >> 16;
+    x *= DOL_DROP_M1;
+    x ^= x >> 15;
+    x *= DOL_DROP_M2;
+    return x >= thr;
+}
+__device__ __forceinline__ bool drop_keep(uint32_t seed_lo, uint32_t seed_hi, uint32_t h,
+                                          uint32_t t_q, uint32_t t_k, uint32_t thr) {
+    return drop_keep_words(drop_row_word(seed_lo, t_q),
+                           drop_col_word(drop_head_word(seed_hi, h), t_k), thr);
+}
+
+// host: keep iff x >= floor(p * 2^32), p taken as the IEEE float32 it is
+static inline uint32_t drop_threshold(float p_drop) {
+    return (uint32_t)((double)p_drop * 4294967296.0);
+}
+static inline bool drop_p_valid(float p_drop) { return p_drop >= 0.f && p_drop < 1.f; }
+
+// ===========================================================================
 // Forward
 // ===========================================================================
 
-template <int DPAD>
+template <int DPAD, bool DROPOUT>
 __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     __bf16* __restrict__ o, float* __restrict__ lse,
     const int32_t* __restrict__ cu, int H, int Hkv, int D, int G,
     int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs, int64_t v_ts, int64_t v_hs,
-    int64_t o_ts, int64_t T_total, float scale) {
+    int64_t o_ts, int64_t T_total, float scale,
+    uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
     constexpr int KCH = DPAD / 32;   // contraction chunks for QK^T
     constexpr int DCH = DPAD / 16;   // output col blocks for PV
     // Strides chosen with tools_lds_sim.py (exact gfx950 bank model):
@@ -299,6 +363,17 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     for (int r = 0; r < 4; ++r) { m_run[r] = -INFINITY; l_run[r] = 0.f; }
 #pragma unroll
     for (int dc = 0; dc < DCH; ++dc) o_acc[dc] = {0.f, 0.f, 0.f, 0.f};
+
+    // dropout: this lane's 4 q rows are fixed for the kernel, so their row
+    // words are hoisted; column words are per key tile (compute_tile)
+    uint32_t drop_rw[4];
+    uint32_t drop_hw = 0;
+    if constexpr (DROPOUT) {
+        drop_hw = drop_head_word(seed_hi, (uint32_t)h);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            drop_rw[r] = drop_row_word(seed_lo, (uint32_t)(s0 + qs + wave * 16 + lg * 4 + r));
+    }
 
     // lane base addresses for the PV tr16 ladder (PI23 row placement; the
     // per-step (rowbase, d0) displacement goes in the ds_read immediate)
@@ -394,6 +469,14 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
         //    force, so exp2f does the zeroing for free.
         const bool edge_tile =
             !((ks + 63 <= qs + wave * 16) && (ks + 64 <= kend) && (qs + wave * 16 + 16 <= L));
+        // dropout touches ONLY the bf16 P written to the strip: the online
+        // softmax (rsum / l_run / m_run, hence lse) sees the undropped e
+        uint32_t drop_cw[4];
+        if constexpr (DROPOUT) {
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb)
+                drop_cw[cb] = drop_col_word(drop_hw, (uint32_t)(s0 + ks + cb * 16 + lr));
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float pv[4];
@@ -416,7 +499,10 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
                 float e = exp2f(pv[cb] - mnew);
-                Pw[(lg * 4 + r) * SV + cb * 16 + lr] = (__bf16)e;
+                float ek = e;
+                if constexpr (DROPOUT)
+                    ek = drop_keep_words(drop_rw[r], drop_cw[cb], drop_thr) ? e : 0.f;
+                Pw[(lg * 4 + r) * SV + cb * 16 + lr] = (__bf16)ek;
                 rsum += e;
             }
             rsum = qwave_reduce_sum(rsum);
@@ -546,6 +632,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         inv_l[r] = (l_run[r] > 0.f) ? 1.f / l_run[r] : 0.f;
+        if constexpr (DROPOUT) inv_l[r] *= drop_rp;  // kept P scaled by 1/(1-p)
         const int qpos = qs + wave * 16 + lg * 4 + r;
         if (lr == 0 && qpos < L)
             lse[(int64_t)h * T_total + s0 + qpos] = (m_run[r] + log2f(l_run[r])) * DOL_LN2;
@@ -562,18 +649,56 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     }
 }
 
-template <int DPAD>
+template <int DPAD, bool DROPOUT>
 static int launch_fa_fwd(hipStream_t stream, const __bf16* q, const __bf16* k, const __bf16* v,
                          __bf16* o, float* lse, const int32_t* cu, int batch, int64_t T,
                          int H, int Hkv, int D, int G,
                          int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs,
-                         int64_t v_ts, int64_t v_hs, int max_tiles, float scale) {
+                         int64_t v_ts, int64_t v_hs, int max_tiles, float scale,
+                         float p_drop, uint64_t seed) {
     dim3 grid(max_tiles, batch, H), block(512);
     size_t shmem = ((size_t)(DPAD <= 96 ? 2 : 1) * 64 * (DPAD + 16) * 2 + 8 * 16 * 72) * sizeof(__bf16);
-    hipLaunchKernelGGL((fa_fwd_kernel<DPAD>), grid, block, shmem, stream,
+    hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT>), grid, block, shmem, stream,
                        q, k, v, o, lse, cu, H, Hkv, D, G,
-                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, (int64_t)H * D, T, scale);
+                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, (int64_t)H * D, T, scale,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), drop_threshold(p_drop),
+                       1.f / (1.f - p_drop));
     return dol_last_error();
+}
+
+// shared by both forward entry points; p_drop == 0 runs the DROPOUT=false
+// instantiations (the dropout-free code)
+static int fa_varlen_fwd_dispatch(dolomite_stream_t stream,
+                                  const void* q, const void* k, const void* v,
+                                  void* o, float* lse,
+                                  const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                  int H, int Hkv, int D, int G,
+                                  int64_t q_tstride, int64_t q_gstride,
+                                  int64_t k_tstride, int64_t k_hstride,
+                                  int64_t v_tstride, int64_t v_hstride,
+                                  float scale, int dtype, float p_drop, uint64_t seed) {
+    if (dtype != DOLOMITE_BF16) return 9010;  // bf16 only (north-star dtype)
+    if (D > 128) return 9011;
+    // grid.x = tiles of the longest sequence; shorter sequences' surplus
+    // workgroups exit on the cu_seqlens check.
+    int max_tiles = (max_seqlen + 127) / 128;
+    hipStream_t s = (hipStream_t)stream;
+#define CASE(DP, DROP)                                                                               \
+    return launch_fa_fwd<DP, DROP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,          \
+                                   (__bf16*)o, lse, cu_seqlens, batch, T, H, Hkv, D, G, q_tstride,   \
+                                   q_gstride, k_tstride, k_hstride, v_tstride, v_hstride, max_tiles, \
+                                   scale, p_drop, seed)
+    if (p_drop > 0.f) {
+        if (D <= 32) CASE(32, true);
+        if (D <= 64) CASE(64, true);
+        if (D <= 96) CASE(96, true);
+        CASE(128, true);
+    }
+    if (D <= 32) CASE(32, false);
+    if (D <= 64) CASE(64, false);
+    if (D <= 96) CASE(96, false);
+    CASE(128, false);
+#undef CASE
 }
 
 extern "C" int dolomite_fa_varlen_fwd(dolomite_stream_t stream,
@@ -585,21 +710,24 @@ extern "C" int dolomite_fa_varlen_fwd(dolomite_stream_t stream,
                                       int64_t k_tstride, int64_t k_hstride,
                                       int64_t v_tstride, int64_t v_hstride,
                                       float scale, int dtype) {
-    if (dtype != DOLOMITE_BF16) return 9010;  // bf16 only (north-star dtype)
-    if (D > 128) return 9011;
-    // grid.x = tiles of the longest sequence; shorter sequences' surplus
-    // workgroups exit on the cu_seqlens check.
-    int max_tiles = (max_seqlen + 127) / 128;
-    hipStream_t s = (hipStream_t)stream;
-#define CASE(DP)                                                                                     \
-    return launch_fa_fwd<DP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v, (__bf16*)o,    \
-                             lse, cu_seqlens, batch, T, H, Hkv, D, G, q_tstride, q_gstride,          \
-                             k_tstride, k_hstride, v_tstride, v_hstride, max_tiles, scale)
-    if (D <= 32) CASE(32);
-    if (D <= 64) CASE(64);
-    if (D <= 96) CASE(96);
-    CASE(128);
-#undef CASE
+    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, batch, max_seqlen, T,
+                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
+                                  v_tstride, v_hstride, scale, dtype, 0.f, 0);
+}
+
+extern "C" int dolomite_fa_varlen_fwd_dropout(dolomite_stream_t stream,
+                                              const void* q, const void* k, const void* v,
+                                              void* o, float* lse,
+                                              const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                              int H, int Hkv, int D, int G,
+                                              int64_t q_tstride, int64_t q_gstride,
+                                              int64_t k_tstride, int64_t k_hstride,
+                                              int64_t v_tstride, int64_t v_hstride,
+                                              float scale, int dtype, float p_drop, uint64_t seed) {
+    if (!drop_p_valid(p_drop)) return 9013;  // p_drop outside [0, 1) (NaN included)
+    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, batch, max_seqlen, T,
+                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
+                                  v_tstride, v_hstride, scale, dtype, p_drop, seed);
 }
 
 // ===========================================================================
@@ -727,14 +855,19 @@ extern "C" int dolomite_fa_bwd_preprocess(dolomite_stream_t stream,
 // Occupancy bound: <=96 head-dim fits the 128-VGPR / 64-KB-LDS budget for
 // 2 workgroups/CU (measured: 128 VGPR, 3 prologue spills); the 128 variant
 // does not (43 spills into the hot loop at the cap) and keeps 1 WG/CU.
-template <int DPAD>
+// Dropout (DROPOUT=true): the P^T strip feeding dV holds M ? P : 0 and dV is
+// scaled by rp = 1/(1-p) once at the store; dS uses the UNDROPPED P with the
+// masked, scaled dP: dS = P * ((M ? dP*rp : 0) - delta) * scale (delta =
+// rowsum(dO*O) already equals sum_j P_ij * dP_ij under dropout).
+template <int DPAD, bool DROPOUT>
 __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     const __bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     float* __restrict__ dk_acc, float* __restrict__ dv_acc,
     const int32_t* __restrict__ cu, int H, int Hkv, int D, int G,
     int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs, int64_t v_ts, int64_t v_hs,
-    int64_t do_ts, int64_t T_total, float scale) {
+    int64_t do_ts, int64_t T_total, float scale,
+    uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
     constexpr int KCH = DPAD / 32;
     constexpr int DCH = DPAD / 16;
 
@@ -792,6 +925,16 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     for (int dc = 0; dc < DCH; ++dc) {
         dvr[dc] = {0.f, 0.f, 0.f, 0.f};
         dkr[dc] = {0.f, 0.f, 0.f, 0.f};
+    }
+
+    // dropout: here a lane owns 4 consecutive KEYS for the whole kernel, so
+    // the column words are the hoisted ones; row words are per q block
+    uint32_t drop_cw[4];
+    if constexpr (DROPOUT) {
+        const uint32_t drop_hw = drop_head_word(seed_hi, (uint32_t)h);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            drop_cw[r] = drop_col_word(drop_hw, (uint32_t)(s0 + ks + wave * 16 + lg * 4 + r));
     }
 
     // lane base addresses for the dK/dV tr16 ladders
@@ -897,12 +1040,20 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
             float lsev = qok ? lse[(int64_t)h * T_total + s0 + qpos] * DOL_LOG2E : 0.f;
             float delv = qok ? delta[(int64_t)h * T_total + s0 + qpos] : 0.f;
             bf16x4 pvv, dsv;
+            uint32_t drop_rw = 0;
+            if constexpr (DROPOUT) drop_rw = drop_row_word(seed_lo, (uint32_t)(s0 + qpos));
             if (__builtin_amdgcn_readfirstlane(full_tile ? 1 : 0)) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float pv = exp2f(st[r] * (scale * DOL_LOG2E) - lsev);
-                    pvv[r] = (__bf16)pv;
-                    dsv[r] = (__bf16)(pv * (dpt[r] - delv) * scale);
+                    if constexpr (DROPOUT) {
+                        const bool keep = drop_keep_words(drop_rw, drop_cw[r], drop_thr);
+                        pvv[r] = (__bf16)(keep ? pv : 0.f);
+                        dsv[r] = (__bf16)(pv * ((keep ? dpt[r] * drop_rp : 0.f) - delv) * scale);
+                    } else {
+                        pvv[r] = (__bf16)pv;
+                        dsv[r] = (__bf16)(pv * (dpt[r] - delv) * scale);
+                    }
                 }
             } else {
 #pragma unroll
@@ -910,9 +1061,16 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
                     const int kpos = ks + wave * 16 + lg * 4 + r;
                     bool ok = qok && kpos < kend && kpos <= qpos;
                     float pv = ok ? exp2f(st[r] * (scale * DOL_LOG2E) - lsev) : 0.f;
-                    float ds = ok ? pv * (dpt[r] - delv) * scale : 0.f;
-                    pvv[r] = (__bf16)pv;
-                    dsv[r] = (__bf16)ds;
+                    if constexpr (DROPOUT) {
+                        const bool keep = drop_keep_words(drop_rw, drop_cw[r], drop_thr);
+                        float ds = ok ? pv * ((keep ? dpt[r] * drop_rp : 0.f) - delv) * scale : 0.f;
+                        pvv[r] = (__bf16)(keep ? pv : 0.f);
+                        dsv[r] = (__bf16)ds;
+                    } else {
+                        float ds = ok ? pv * (dpt[r] - delv) * scale : 0.f;
+                        pvv[r] = (__bf16)pv;
+                        dsv[r] = (__bf16)ds;
+                    }
                 }
             }
             const int srow = PI23(cb * 16 + lr) * STS + wave * 16 + lg * 4;
@@ -995,20 +1153,28 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
                 // not evict the XCD-resident Q/dO slices (PMC: dkv read
                 // traffic 3.6 GB/launch vs ~1.4 GB ideal with plain stores)
                 __builtin_nontemporal_store(dkr[dc][r], &dk_acc[idx]);
-                __builtin_nontemporal_store(dvr[dc][r], &dv_acc[idx]);
+                if constexpr (DROPOUT)
+                    __builtin_nontemporal_store(dvr[dc][r] * drop_rp, &dv_acc[idx]);
+                else
+                    __builtin_nontemporal_store(dvr[dc][r], &dv_acc[idx]);
             }
         }
     }
 }
 
-template <int DPAD>
-__global__ void __launch_bounds__(512, 4) fa_bwd_dq_kernel(
+// Occupancy bound: the dropout-free DPAD=128 variant already sits at the
+// 128-VGPR cap (4 spills); the mask words push the DROPOUT one to 10 spills
+// under that cap, so it alone takes the looser 1-workgroup/CU bound and
+// compiles spill-free. Every other instantiation keeps (512, 4).
+template <int DPAD, bool DROPOUT>
+__global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     const __bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     __bf16* __restrict__ dqkv_q,
     const int32_t* __restrict__ cu, int H, int Hkv, int D, int G,
     int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs, int64_t v_ts, int64_t v_hs,
-    int64_t do_ts, int64_t T_total, float scale) {
+    int64_t do_ts, int64_t T_total, float scale,
+    uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
     constexpr int KCH = DPAD / 32;
     constexpr int DCH = DPAD / 16;
     constexpr int ST = 64 + 8;                 // strip stride
@@ -1076,6 +1242,17 @@ __global__ void __launch_bounds__(512, 4) fa_bwd_dq_kernel(
     f32x4 dq[DCH];
 #pragma unroll
     for (int dc = 0; dc < DCH; ++dc) dq[dc] = {0.f, 0.f, 0.f, 0.f};
+
+    // dropout: same dS formula as dkv with the fwd-style lane mapping (4 q
+    // rows fixed per lane -> hoisted row words; column words per key block)
+    uint32_t drop_rw[4];
+    uint32_t drop_hw = 0;
+    if constexpr (DROPOUT) {
+        drop_hw = drop_head_word(seed_hi, (uint32_t)h);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            drop_rw[r] = drop_row_word(seed_lo, (uint32_t)(s0 + qs + wave * 16 + lg * 4 + r));
+    }
 
     if (D < DPAD) {  // pad columns zeroed once (see dkv note)
         for (int pidx = threadIdx.x; pidx < 64 * (DPAD - D) / 8; pidx += 512) {
@@ -1153,11 +1330,16 @@ __global__ void __launch_bounds__(512, 4) fa_bwd_dq_kernel(
                 bf16x8 vb = *(const bf16x8*)&Vlds[(cb * 16 + lr) * SQ + d0];
                 dp = MFMA16(dfr[kc], vb, dp);
             }
+            uint32_t drop_cw = 0;
+            if constexpr (DROPOUT) drop_cw = drop_col_word(drop_hw, (uint32_t)(s0 + ks + cb * 16 + lr));
             if (__builtin_amdgcn_readfirstlane(full_tile ? 1 : 0)) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float pv = exp2f(sc[r] * (scale * DOL_LOG2E) - lsev[r]);
-                    dSw[(lg * 4 + r) * ST + cb * 16 + lr] = (__bf16)(pv * (dp[r] - delv[r]) * scale);
+                    float dpm = dp[r];
+                    if constexpr (DROPOUT)
+                        dpm = drop_keep_words(drop_rw[r], drop_cw, drop_thr) ? dp[r] * drop_rp : 0.f;
+                    dSw[(lg * 4 + r) * ST + cb * 16 + lr] = (__bf16)(pv * (dpm - delv[r]) * scale);
                 }
             } else {
 #pragma unroll
@@ -1166,7 +1348,10 @@ __global__ void __launch_bounds__(512, 4) fa_bwd_dq_kernel(
                     const int kpos = ks + cb * 16 + lr;
                     bool ok = qpos < L && kpos < kend_total && kpos <= qpos;
                     float pv = ok ? exp2f(sc[r] * (scale * DOL_LOG2E) - lsev[r]) : 0.f;
-                    float ds = ok ? pv * (dp[r] - delv[r]) * scale : 0.f;
+                    float dpm = dp[r];
+                    if constexpr (DROPOUT)
+                        dpm = drop_keep_words(drop_rw[r], drop_cw, drop_thr) ? dp[r] * drop_rp : 0.f;
+                    float ds = ok ? pv * (dpm - delv[r]) * scale : 0.f;
                     dSw[(lg * 4 + r) * ST + cb * 16 + lr] = (__bf16)ds;
                 }
             }
@@ -1224,28 +1409,69 @@ __global__ void __launch_bounds__(512, 4) fa_bwd_dq_kernel(
     }
 }
 
-template <int DPAD>
+template <int DPAD, bool DROPOUT>
 static int launch_fa_bwd(hipStream_t stream, const __bf16* q, const __bf16* k, const __bf16* v,
                          const __bf16* dout, const float* lse, const float* delta,
                          __bf16* dqkv_q, float* dk_acc, float* dv_acc,
                          const int32_t* cu, int batch, int64_t T, int H, int Hkv, int D, int G,
                          int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs,
-                         int64_t v_ts, int64_t v_hs, int64_t do_ts, int max_tiles, float scale) {
+                         int64_t v_ts, int64_t v_hs, int64_t do_ts, int max_tiles, float scale,
+                         float p_drop, uint64_t seed) {
     constexpr int ST = 64 + 8;
     dim3 block(512);
     dim3 grid(max_tiles, batch, H);
     constexpr int SQ = DPAD + 16;
+    const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
+    const uint32_t thr = drop_threshold(p_drop);
+    const float rp = 1.f / (1.f - p_drop);
     size_t shmem_dkv = (size_t)(64 * (128 + 4) * 2 + 64 * SQ * 2) * sizeof(__bf16);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<DPAD>), grid, block, shmem_dkv, stream,
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<DPAD, DROPOUT>), grid, block, shmem_dkv, stream,
                        q, k, v, dout, lse, delta, dk_acc, dv_acc, cu, H, Hkv, D, G,
-                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale);
+                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
+                       seed_lo, seed_hi, thr, rp);
     int err = dol_last_error();
     if (err) return err;
     size_t shmem_dq = (size_t)(64 * SQ * 2 + 8 * 16 * ST) * sizeof(__bf16);
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD>), grid, block, shmem_dq, stream,
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD, DROPOUT>), grid, block, shmem_dq, stream,
                        q, k, v, dout, lse, delta, dqkv_q, cu, H, Hkv, D, G,
-                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale);
+                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
+                       seed_lo, seed_hi, thr, rp);
     return dol_last_error();
+}
+
+// shared by both backward entry points (see fa_varlen_fwd_dispatch)
+static int fa_varlen_bwd_dispatch(dolomite_stream_t stream,
+                                  const void* q, const void* k, const void* v,
+                                  const void* dout, const float* lse,
+                                  const float* delta, void* dqkv_q, float* dk_acc, float* dv_acc,
+                                  const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                  int H, int Hkv, int D, int G,
+                                  int64_t q_tstride, int64_t q_gstride,
+                                  int64_t k_tstride, int64_t k_hstride,
+                                  int64_t v_tstride, int64_t v_hstride,
+                                  int64_t do_tstride,
+                                  float scale, int dtype, float p_drop, uint64_t seed) {
+    if (dtype != DOLOMITE_BF16) return 9010;
+    if (D > 128) return 9011;
+    int max_tiles = (max_seqlen + 127) / 128;
+    hipStream_t s = (hipStream_t)stream;
+#define CASE(DP, DROP)                                                                                  \
+    return launch_fa_bwd<DP, DROP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,             \
+                                   (const __bf16*)dout, lse, delta, (__bf16*)dqkv_q, dk_acc, dv_acc,    \
+                                   cu_seqlens, batch, T, H, Hkv, D, G, q_tstride, q_gstride, k_tstride, \
+                                   k_hstride, v_tstride, v_hstride, do_tstride, max_tiles, scale,       \
+                                   p_drop, seed)
+    if (p_drop > 0.f) {
+        if (D <= 32) CASE(32, true);
+        if (D <= 64) CASE(64, true);
+        if (D <= 96) CASE(96, true);
+        CASE(128, true);
+    }
+    if (D <= 32) CASE(32, false);
+    if (D <= 64) CASE(64, false);
+    if (D <= 96) CASE(96, false);
+    CASE(128, false);
+#undef CASE
 }
 
 extern "C" int dolomite_fa_varlen_bwd(dolomite_stream_t stream,
@@ -1259,20 +1485,58 @@ extern "C" int dolomite_fa_varlen_bwd(dolomite_stream_t stream,
                                       int64_t v_tstride, int64_t v_hstride,
                                       int64_t do_tstride,
                                       float scale, int dtype) {
-    if (dtype != DOLOMITE_BF16) return 9010;
-    if (D > 128) return 9011;
-    int max_tiles = (max_seqlen + 127) / 128;
-    hipStream_t s = (hipStream_t)stream;
-#define CASE(DP)                                                                                        \
-    return launch_fa_bwd<DP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,                   \
-                             (const __bf16*)dout, lse, delta, (__bf16*)dqkv_q, dk_acc, dv_acc,          \
-                             cu_seqlens, batch, T, H, Hkv, D, G, q_tstride, q_gstride, k_tstride,       \
-                             k_hstride, v_tstride, v_hstride, do_tstride, max_tiles, scale)
-    if (D <= 32) CASE(32);
-    if (D <= 64) CASE(64);
-    if (D <= 96) CASE(96);
-    CASE(128);
-#undef CASE
+    return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
+                                  cu_seqlens, batch, max_seqlen, T, H, Hkv, D, G,
+                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
+                                  do_tstride, scale, dtype, 0.f, 0);
+}
+
+extern "C" int dolomite_fa_varlen_bwd_dropout(dolomite_stream_t stream,
+                                              const void* q, const void* k, const void* v,
+                                              const void* dout, const float* lse,
+                                              const float* delta, void* dqkv_q, float* dk_acc, float* dv_acc,
+                                              const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                              int H, int Hkv, int D, int G,
+                                              int64_t q_tstride, int64_t q_gstride,
+                                              int64_t k_tstride, int64_t k_hstride,
+                                              int64_t v_tstride, int64_t v_hstride,
+                                              int64_t do_tstride,
+                                              float scale, int dtype, float p_drop, uint64_t seed) {
+    if (!drop_p_valid(p_drop)) return 9013;
+    return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
+                                  cu_seqlens, batch, max_seqlen, T, H, Hkv, D, G,
+                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
+                                  do_tstride, scale, dtype, p_drop, seed);
+}
+
+// Keep-mask probe: out[(h*nq + i)*nk + j] = keep(seed, h, tq0+i, tk0+j) as
+// 0/1 bytes, through the same device function the attention kernels use
+// (the host compares against the Python restatement bit for bit).
+__global__ void __launch_bounds__(256) fa_dropout_mask_probe_kernel(
+    uint8_t* __restrict__ out, uint32_t seed_lo, uint32_t seed_hi, uint32_t thr,
+    int64_t total, int64_t tq0, int nq, int64_t tk0, int nk) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int j = (int)(idx % nk);
+    const int64_t hi = idx / nk;
+    const int i = (int)(hi % nq);
+    const uint32_t h = (uint32_t)(hi / nq);
+    out[idx] = drop_keep(seed_lo, seed_hi, h, (uint32_t)(tq0 + i), (uint32_t)(tk0 + j), thr) ? 1 : 0;
+}
+
+extern "C" int dolomite_fa_dropout_mask_probe(dolomite_stream_t stream, uint8_t* out,
+                                              uint64_t seed, float p_drop, int H,
+                                              int64_t tq0, int nq, int64_t tk0, int nk) {
+    if (!drop_p_valid(p_drop)) return 9013;
+    if (H < 0 || nq < 0 || nk < 0) return 9014;
+    const int64_t total = (int64_t)H * nq * nk;
+    if (total == 0) return 0;
+    const int64_t nblocks = (total + 255) / 256;
+    if (nblocks > 0x7fffffff) return 9014;
+    hipLaunchKernelGGL(fa_dropout_mask_probe_kernel, dim3((uint32_t)nblocks), dim3(256), 0,
+                       (hipStream_t)stream, out, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       drop_threshold(p_drop), total, tq0, nq, tk0, nk);
+    return dol_last_error();
 }
 
 // ===========================================================================

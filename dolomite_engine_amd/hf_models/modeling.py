@@ -280,13 +280,16 @@ class Attention(nn.Module):
 
     # ---- padding-free packed path (the hot path) ----
     def forward_padding_free(self, hidden_states, rope_cos_sin, cu_seqlens, max_seqlen):
-        if self.training and self.attn_pdrop > 0:
-            raise NotImplementedError("attention dropout > 0 is not supported on the padding-free path")
         qkv = self.c_attn(hidden_states)
         if self.position_embedding_type == "rope":
             cos, sin = rope_cos_sin  # (T, D) fp32
             qkv = rope_packed_qkv(qkv, cos, sin, self.layout)
-        attn_output = varlen_attention(qkv, cu_seqlens, max_seqlen, self.layout, self.softmax_scale)
+        # attention dropout is fused into the flash kernels (padding_free.py:49-59
+        # forwards dropout_p to flash_attn_varlen_func the same way)
+        attn_output = varlen_attention(
+            qkv, cu_seqlens, max_seqlen, self.layout, self.softmax_scale,
+            dropout_p=self.attn_pdrop if self.training else 0.0,
+        )
         attn_output = self.c_proj(attn_output)
         return self.resid_dropout(attn_output)
 

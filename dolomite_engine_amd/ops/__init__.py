@@ -3,6 +3,8 @@
 from .functional import (
     QKVLayout,
     adamw_step_flat,
+    attention_dropout_keep_mask,
+    draw_attention_dropout_seed,
     fused_cross_entropy,
     fused_layernorm,
     fused_rmsnorm,

@@ -342,7 +342,64 @@ def rope_packed_qkv(qkv, cos, sin, layout: QKVLayout):
 # ---------------------------------------------------------------------------
 
 
-def _attn_fwd_cpu(qkv, cu, scale, lo: QKVLayout):
+_U32 = 0xFFFFFFFF
+_DROP_CQ, _DROP_CK, _DROP_CH = 0x9E3779B1, 0x85EBCA77, 0xC2B2AE3D
+_DROP_M1, _DROP_M2 = 0x7FEB352D, 0x846CA68B
+
+
+def _drop_mix32(x: torch.Tensor) -> torch.Tensor:
+    """The 32-bit avalanche mixer of the keep-mask on int64 lanes (values
+    stay in [0, 2^32); int64 products wrap, the low 32 bits are exact)."""
+    x = x ^ (x >> 16)
+    x = (x * _DROP_M1) & _U32
+    x = x ^ (x >> 15)
+    x = (x * _DROP_M2) & _U32
+    return x ^ (x >> 16)
+
+
+def attention_dropout_threshold(p: float) -> int:
+    """floor(p * 2^32) with p taken as the IEEE float32 the C-ABI receives."""
+    p32 = float(torch.tensor(float(p), dtype=torch.float32))
+    return int(p32 * 4294967296.0)
+
+
+def attention_dropout_keep_mask(seed: int, H: int, tq, tk, p: float) -> torch.Tensor:
+    """Attention-dropout keep mask, the torch-int64 restatement of the device
+    function in csrc/attention.hip (definition: include/dolomite_hip.h).
+
+    tq / tk: 1-D integer tensors of GLOBAL packed token indices. Returns a
+    bool (H, len(tq), len(tk)) tensor on CPU: True = kept. Pure function of
+    its arguments — the same bits the fwd/dkv/dq kernels regenerate."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed_lo, seed_hi = seed & _U32, seed >> 32
+    tq = torch.as_tensor(tq, dtype=torch.int64).cpu() & _U32
+    tk = torch.as_tensor(tk, dtype=torch.int64).cpu() & _U32
+    h = torch.arange(H, dtype=torch.int64)
+    rw = _drop_mix32(((tq * _DROP_CQ) & _U32) ^ seed_lo)                    # (nq,)
+    hw = _drop_mix32(((h * _DROP_CH) & _U32) ^ seed_hi)                     # (H,)
+    cw = _drop_mix32(((tk * _DROP_CK) & _U32)[None, :] ^ hw[:, None])       # (H, nk)
+    x = rw[None, :, None] ^ cw[:, None, :]
+    x = x ^ (x >> 16)
+    x = (x * _DROP_M1) & _U32
+    x = x ^ (x >> 15)
+    x = (x * _DROP_M2) & _U32
+    return x >= attention_dropout_threshold(p)
+
+
+def draw_attention_dropout_seed() -> int:
+    """One int64 from torch's default CPU generator: no device sync, restored
+    with the checkpointed torch RNG state (bit-exact resume), and replayed by
+    torch.utils.checkpoint's preserve_rng_state during block recompute."""
+    return int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64))
+
+
+def _drop_scale(p: float) -> float:
+    """1/(1-p) as the kernels compute it (float32 arithmetic)."""
+    one = torch.tensor(1.0, dtype=torch.float32)
+    return float(one / (one - torch.tensor(float(p), dtype=torch.float32)))
+
+
+def _attn_fwd_cpu(qkv, cu, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
     """fp32-softmax varlen attention + lse, CPU restatement of the kernel."""
     q, k, v = lo.unpack_cpu(qkv)
     T = q.shape[0]
@@ -358,6 +415,10 @@ def _attn_fwd_cpu(qkv, cu, scale, lo: QKVLayout):
         vi = v[s:e].float()
         L = e - s
         mask = torch.ones(L, L, dtype=torch.bool).tril()
+        if dropout_p > 0:
+            tok = torch.arange(s, e)
+            keep = attention_dropout_keep_mask(seed, lo.H, tok, tok, dropout_p)
+            rp = _drop_scale(dropout_p)
         for h in range(lo.H):
             j = h // (lo.H // lo.Hkv) if lo.Hkv > 1 else 0
             sc = (qi[:, h] @ ki[:, j].T) * scale
@@ -366,7 +427,10 @@ def _attn_fwd_cpu(qkv, cu, scale, lo: QKVLayout):
             p = (sc - m).exp()
             l = p.sum(-1, keepdim=True)
             lse[h, s:e] = (m + l.log()).squeeze(-1)
-            o[s:e, h * lo.D : (h + 1) * lo.D] = ((p / l) @ vi[:, j]).to(qkv.dtype)
+            pn = p / l
+            if dropout_p > 0:  # lse / the softmax itself are undropped
+                pn = pn * keep[h] * rp
+            o[s:e, h * lo.D : (h + 1) * lo.D] = (pn @ vi[:, j]).to(qkv.dtype)
     return o, lse
 
 
@@ -376,32 +440,39 @@ class VarlenAttention(torch.autograd.Function):
     o (T, H*D). LSE saved for the recompute backward."""
 
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen: int, layout: QKVLayout, scale: float):
+    def forward(ctx, qkv, cu_seqlens, max_seqlen: int, layout: QKVLayout, scale: float,
+                dropout_p: float = 0.0, seed: int = 0):
         lo = layout
         T = qkv.shape[0]
         batch = cu_seqlens.shape[0] - 1
+        dropout_p = float(dropout_p)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         if qkv.is_cuda:
             qkv = qkv.contiguous()
             o = torch.empty(T, lo.H * lo.D, dtype=qkv.dtype, device=qkv.device)
             lse = torch.empty(lo.H, T, dtype=torch.float32, device=qkv.device)
-            with hip.prof("fa_varlen_fwd"):
-             hip.check(
-                hip.lib().dolomite_fa_varlen_fwd(
-                    hip.stream(),
-                    hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
-                    hip.ptr(o), hip.ptr(lse), hip.ptr(cu_seqlens),
-                    batch, int(max_seqlen), T, lo.H, lo.Hkv, lo.D, lo.G,
-                    lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
-                    lo.row_len, lo.kv_hstride, float(scale), hip.dt(qkv),
-                ),
-                "fa_varlen_fwd",
+            args = (
+                hip.stream(),
+                hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
+                hip.ptr(o), hip.ptr(lse), hip.ptr(cu_seqlens),
+                batch, int(max_seqlen), T, lo.H, lo.Hkv, lo.D, lo.G,
+                lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
+                lo.row_len, lo.kv_hstride, float(scale), hip.dt(qkv),
             )
+            with hip.prof("fa_varlen_fwd"):
+                if dropout_p > 0:
+                    hip.check(hip.lib().dolomite_fa_varlen_fwd_dropout(*args, dropout_p, seed),
+                              "fa_varlen_fwd_dropout")
+                else:
+                    hip.check(hip.lib().dolomite_fa_varlen_fwd(*args), "fa_varlen_fwd")
         else:
-            o, lse = _attn_fwd_cpu(qkv, cu_seqlens, scale, lo)
+            o, lse = _attn_fwd_cpu(qkv, cu_seqlens, scale, lo, dropout_p, seed)
         ctx.save_for_backward(qkv, o, lse, cu_seqlens)
         ctx.layout = lo
         ctx.scale = scale
         ctx.max_seqlen = int(max_seqlen)
+        ctx.dropout_p = dropout_p
+        ctx.seed = seed
         return o
 
     @staticmethod
@@ -425,19 +496,21 @@ class VarlenAttention(torch.autograd.Function):
             dk_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
             dv_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
             dqkv = torch.empty_like(qkv)
-            with hip.prof("fa_varlen_bwd"):
-             hip.check(
-                hip.lib().dolomite_fa_varlen_bwd(
-                    hip.stream(),
-                    hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
-                    hip.ptr(dout), hip.ptr(lse), hip.ptr(delta), hip.ptr(dqkv),
-                    hip.ptr(dk_acc), hip.ptr(dv_acc),
-                    hip.ptr(cu), batch, ctx.max_seqlen, T, lo.H, lo.Hkv, lo.D, lo.G,
-                    lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
-                    lo.row_len, lo.kv_hstride, lo.H * lo.D, float(ctx.scale), hip.dt(qkv),
-                ),
-                "fa_varlen_bwd",
+            args = (
+                hip.stream(),
+                hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
+                hip.ptr(dout), hip.ptr(lse), hip.ptr(delta), hip.ptr(dqkv),
+                hip.ptr(dk_acc), hip.ptr(dv_acc),
+                hip.ptr(cu), batch, ctx.max_seqlen, T, lo.H, lo.Hkv, lo.D, lo.G,
+                lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
+                lo.row_len, lo.kv_hstride, lo.H * lo.D, float(ctx.scale), hip.dt(qkv),
             )
+            with hip.prof("fa_varlen_bwd"):
+                if ctx.dropout_p > 0:
+                    hip.check(hip.lib().dolomite_fa_varlen_bwd_dropout(*args, ctx.dropout_p, ctx.seed),
+                              "fa_varlen_bwd_dropout")
+                else:
+                    hip.check(hip.lib().dolomite_fa_varlen_bwd(*args), "fa_varlen_bwd")
             hip.check(
                 hip.lib().dolomite_fa_grad_finalize(
                     hip.stream(), hip.ptr(dk_acc), hip.ptr(dv_acc), hip.ptr(dqkv),
@@ -446,16 +519,16 @@ class VarlenAttention(torch.autograd.Function):
                 ),
                 "fa_grad_finalize",
             )
-            return dqkv, None, None, None, None
+            return dqkv, None, None, None, None, None, None
         # CPU: differentiate the CPU restatement with torch autograd
         qkv_l = qkv.detach().requires_grad_(True)
         with torch.enable_grad():
-            o2, _ = _attn_fwd_cpu_autograd(qkv_l, cu, ctx.scale, lo)
+            o2, _ = _attn_fwd_cpu_autograd(qkv_l, cu, ctx.scale, lo, ctx.dropout_p, ctx.seed)
             (dqkv,) = torch.autograd.grad(o2, qkv_l, dout)
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
-def _attn_fwd_cpu_autograd(qkv, cu, scale, lo: QKVLayout):
+def _attn_fwd_cpu_autograd(qkv, cu, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
     q, k, v = lo.unpack_cpu(qkv)
     T = q.shape[0]
     outs = []
@@ -470,20 +543,38 @@ def _attn_fwd_cpu_autograd(qkv, cu, scale, lo: QKVLayout):
         vi = v[s:e].float()
         L = e - s
         mask = torch.ones(L, L, dtype=torch.bool).tril()
+        if dropout_p > 0:
+            tok = torch.arange(s, e)
+            keep = attention_dropout_keep_mask(seed, lo.H, tok, tok, dropout_p)
+            rp = _drop_scale(dropout_p)
         hs = []
         for h in range(lo.H):
             j = h // (lo.H // lo.Hkv) if lo.Hkv > 1 else 0
             sc = (qi[:, h] @ ki[:, j].T) * scale
             sc = sc.masked_fill(~mask, float("-inf"))
             p = torch.softmax(sc, dim=-1)
+            if dropout_p > 0:
+                p = p * keep[h] * rp
             hs.append(p @ vi[:, j])
         pieces.append(torch.cat(hs, dim=-1).to(qkv.dtype))
     o = torch.cat(pieces, dim=0)
     return o, None
 
 
-def varlen_attention(qkv, cu_seqlens, max_seqlen, layout: QKVLayout, scale: float):
-    return VarlenAttention.apply(qkv, cu_seqlens, int(max_seqlen), layout, scale)
+def varlen_attention(qkv, cu_seqlens, max_seqlen, layout: QKVLayout, scale: float,
+                     dropout_p: float = 0.0, seed: int | None = None):
+    """Causal varlen attention on the packed qkv. dropout_p > 0 drops
+    attention probabilities with the counter-based keep mask
+    (attention_dropout_keep_mask); seed=None draws one from torch's default
+    CPU generator (draw_attention_dropout_seed)."""
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
+    if dropout_p == 0.0:  # no draw: the RNG stream of p = 0 runs is untouched
+        return VarlenAttention.apply(qkv, cu_seqlens, int(max_seqlen), layout, scale, 0.0, 0)
+    if seed is None:
+        seed = draw_attention_dropout_seed()
+    return VarlenAttention.apply(qkv, cu_seqlens, int(max_seqlen), layout, scale, dropout_p, int(seed))
 
 
 # ---------------------------------------------------------------------------

@@ -22,6 +22,7 @@ BF16 = 1
 _c = ctypes
 _i32 = _c.c_int32
 _i64 = _c.c_int64
+_u64 = _c.c_uint64
 _f32 = _c.c_float
 _p = _c.c_void_p
 
@@ -46,6 +47,18 @@ _SIGNATURES = {
          _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
         _i32,
     ),
+    # the two entry points above + (float p_drop, uint64_t seed)
+    "dolomite_fa_varlen_fwd_dropout": (
+        [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
+        _i32,
+    ),
+    "dolomite_fa_varlen_bwd_dropout": (
+        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
+        _i32,
+    ),
+    "dolomite_fa_dropout_mask_probe": ([_p, _p, _u64, _f32, _i32, _i64, _i32, _i64, _i32], _i32),
     "dolomite_fa_grad_finalize": ([_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32], _i32),
     "dolomite_ce_fwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),
     "dolomite_ce_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),

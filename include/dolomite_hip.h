@@ -111,8 +111,9 @@ int dolomite_rope_qkv(dolomite_stream_t stream,
  * (this addresses the packed c_attn output without copies for MHA/GQA/MQA)
  * o: (T, H*D) row-major contiguous bf16/fp32; lse: (H, T) fp32 log-sum-exp
  * (natural log, includes softmax scale), for backward.
- * cu_seqlens: (batch+1,) int32 device pointer; causal only; dropout
- * unsupported (training configs on this path run attn_pdrop = 0).
+ * cu_seqlens: (batch+1,) int32 device pointer; causal only. Attention
+ * dropout: the *_dropout entry points below.
+ * Error codes: 9010 dtype != bf16, 9011 D > 128.
  * ---------------------------------------------------------------------- */
 int dolomite_fa_varlen_fwd(dolomite_stream_t stream,
                            const void* q, const void* k, const void* v,
@@ -159,6 +160,64 @@ int dolomite_fa_grad_finalize(dolomite_stream_t stream,
                               void* dqkv, int64_t T, int Hkv, int D, int G,
                               int64_t row_tstride,
                               int64_t k_off, int64_t kv_hstride, int64_t v_off, int dtype);
+
+/* ------------------------------------------------------------------------
+ * Attention dropout (flash_attn_varlen_func's dropout_p, forwarded by the
+ * reference at attention/padding_free.py:49-59), fused into the kernels.
+ *
+ * Keep-mask: a pure counter-based function, never written to memory — the
+ * forward and both backward kernels regenerate it. All arithmetic is
+ * unsigned 32-bit (wrapping):
+ *   mix(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;
+ *            x *= 0x846CA68B;  x ^= x >> 16
+ *   seed_lo = seed & 0xFFFFFFFF,  seed_hi = seed >> 32
+ *   rw = mix(seed_lo ^ (t_q * 0x9E3779B1))                  per-row word
+ *   hw = mix(seed_hi ^ (h   * 0xC2B2AE3D))                  per-head word
+ *   cw = mix(hw      ^ (t_k * 0x85EBCA77))                  per-column word
+ *   x  = rw ^ cw;  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;
+ *   x *= 0x846CA68B                      (mix without its last xorshift)
+ *   keep(seed, h, t_q, t_k, p) = x >= floor(p * 2^32)
+ * h is the q-head; t_q / t_k are GLOBAL packed token indices
+ * (cu_seqlens[b] + position, low 32 bits), so the mask depends neither on
+ * tile geometry nor on which kernel asks. p is the IEEE float32 p_drop
+ * (floor(p * 2^32) is exact in double). Kept probabilities are scaled by
+ * 1/(1-p) (float32); lse is the UNDROPPED log-sum-exp. The Python
+ * restatement is ops/functional.py attention_dropout_keep_mask.
+ *
+ * Same argument lists and error codes as dolomite_fa_varlen_fwd / _bwd,
+ * plus (p_drop, seed); error 9013 for p_drop outside [0, 1) (NaN included).
+ * p_drop == 0 runs exactly the dropout-free kernels. The backward must get
+ * the p_drop and seed of its forward; preprocess and grad_finalize are
+ * unchanged (delta = rowsum(dO*O) holds under dropout).
+ * ---------------------------------------------------------------------- */
+int dolomite_fa_varlen_fwd_dropout(dolomite_stream_t stream,
+                                   const void* q, const void* k, const void* v,
+                                   void* o, float* lse,
+                                   const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                   int H, int Hkv, int D, int G,
+                                   int64_t q_tstride, int64_t q_gstride,
+                                   int64_t k_tstride, int64_t k_hstride,
+                                   int64_t v_tstride, int64_t v_hstride,
+                                   float scale, int dtype, float p_drop, uint64_t seed);
+int dolomite_fa_varlen_bwd_dropout(dolomite_stream_t stream,
+                                   const void* q, const void* k, const void* v,
+                                   const void* dout, const float* lse,
+                                   const float* delta, void* dqkv_q, float* dk_acc, float* dv_acc,
+                                   const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                   int H, int Hkv, int D, int G,
+                                   int64_t q_tstride, int64_t q_gstride,
+                                   int64_t k_tstride, int64_t k_hstride,
+                                   int64_t v_tstride, int64_t v_hstride,
+                                   int64_t do_tstride,
+                                   float scale, int dtype, float p_drop, uint64_t seed);
+
+/* Keep-mask probe: out[(h*nq + i)*nk + j] = keep(seed, h, tq0+i, tk0+j, p_drop)
+ * as 0/1 bytes for h in [0, H), through the device function the attention
+ * kernels use. out: (H, nq, nk) uint8 device pointer. Errors: 9013 as above,
+ * 9014 for a negative or oversized box. */
+int dolomite_fa_dropout_mask_probe(dolomite_stream_t stream, uint8_t* out,
+                                   uint64_t seed, float p_drop, int H,
+                                   int64_t tq0, int nq, int64_t tk0, int nk);
 
 /* MFMA fragment-layout self-test: computes C = A(16x32) @ B(32x16) with the
  * compiled fragment mapping; host verifies against a CPU matmul.
