@@ -486,35 +486,81 @@ extern "C" int dolomite_layernorm_bwd(dolomite_stream_t stream,
 }
 
 // ===========================================================================
-// Partials reduction: out[h] = sum_i partial[i*H + h].
-// Parallel over column blocks AND row chunks (atomic join); `out` must be
-// zero-initialized by the caller. (The serial column-loop version filled
-// only H/256 workgroups: 40 GB/s on (4096, 2560).)
+// Partials reduction: out[h] = sum_i partial[i*H + h], in a FIXED order (no
+// atomics, so dw/db are bitwise reproducible run to run):
+//   nsplit = min(32, ceil(nblocks / 128)),  chunk = ceil(nblocks / nsplit)
+//   pass 1: thread (c, h) sums rows [c*chunk, min((c+1)*chunk, nblocks)) of
+//           column h in ascending row order, starting from +0, and stores
+//           the sum over partial[c*chunk*H + h] — the first element it read,
+//           which no other thread touches;
+//   pass 2: out[h] = the chunk sums added in ascending c, starting from +0.
+// nsplit == 1 is pass 1 alone, storing straight into out (partial is then
+// left intact). No chunk is empty: nblocks > 128*(nsplit-1) and, when the cap
+// of 32 binds, nblocks > 31*31, so (nsplit-1)*chunk < nblocks either way.
+// The C signature keeps `const float* partial` (ABI unchanged); the buffer
+// is the caller's mutable scratch and the header says it is overwritten.
+// Parallel over column blocks AND row chunks: the serial column-loop
+// version filled only H/256 workgroups, 40 GB/s on (4096, 2560).
 // ===========================================================================
 
-__global__ void __launch_bounds__(256) reduce_partials_kernel(
-    const float* __restrict__ partial, float* __restrict__ out, int64_t nblocks, int64_t H) {
+#define REDUCE_MAX_SPLIT 32
+#define REDUCE_ROWS_PER_SPLIT 128
+
+__global__ void __launch_bounds__(256) reduce_partials_chunk_kernel(
+    float* partial, float* out, int64_t nblocks, int64_t H, int64_t chunk) {
     int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= H) return;
-    int64_t chunk = (nblocks + gridDim.y - 1) / gridDim.y;
     int64_t i0 = (int64_t)blockIdx.y * chunk;
     int64_t i1 = min(i0 + chunk, nblocks);
+    const float* p = partial + h;
     float acc = 0.f;
-    for (int64_t i = i0; i < i1; ++i) acc += partial[i * H + h];
+    int64_t i = i0;
+    // 8 independent loads in flight, then 8 adds in row order
+    for (; i + 8 <= i1; i += 8) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = p[(i + k) * H];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc += v[k];
+    }
+    for (; i < i1; ++i) acc += p[i * H];
     if (gridDim.y == 1)
         out[h] = acc;
-    else
-        atomicAdd(&out[h], acc);
+    else if (i0 < i1)  // always true (no chunk is empty); keeps the store in bounds regardless
+        partial[i0 * H + h] = acc;
+}
+
+__global__ void __launch_bounds__(256) reduce_partials_fold_kernel(
+    const float* __restrict__ partial, float* __restrict__ out,
+    int64_t H, int64_t chunk, int nsplit) {
+    int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= H) return;
+    float v[REDUCE_MAX_SPLIT];
+#pragma unroll
+    for (int c = 0; c < REDUCE_MAX_SPLIT; ++c)
+        v[c] = c < nsplit ? partial[(int64_t)c * chunk * H + h] : 0.f;
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < REDUCE_MAX_SPLIT; ++c)
+        if (c < nsplit) acc += v[c];
+    out[h] = acc;
 }
 
 extern "C" int dolomite_reduce_partials(dolomite_stream_t stream,
                                         const float* partial, float* out,
                                         int64_t nblocks, int64_t H) {
-    int64_t nsplit64 = (nblocks + 127) / 128;
-    uint32_t nsplit = (uint32_t)(nsplit64 > 32 ? 32 : nsplit64);
+    if (H <= 0) return 0;
+    float* scratch = const_cast<float*>(partial);
+    int64_t nsplit64 = (nblocks + REDUCE_ROWS_PER_SPLIT - 1) / REDUCE_ROWS_PER_SPLIT;
+    int nsplit = (int)(nsplit64 > REDUCE_MAX_SPLIT ? REDUCE_MAX_SPLIT : nsplit64);
     if (nsplit < 1) nsplit = 1;
-    dim3 grid((uint32_t)((H + 255) / 256), nsplit), block(256);
-    hipLaunchKernelGGL(reduce_partials_kernel, grid, block, 0, (hipStream_t)stream, partial, out, nblocks, H);
+    int64_t chunk = (nblocks + nsplit - 1) / nsplit;
+    dim3 grid((uint32_t)((H + 255) / 256), (uint32_t)nsplit), block(256);
+    hipLaunchKernelGGL(reduce_partials_chunk_kernel, grid, block, 0, (hipStream_t)stream,
+                       scratch, out, nblocks, H, chunk);
+    if (nsplit > 1)
+        hipLaunchKernelGGL(reduce_partials_fold_kernel, dim3(grid.x), block, 0, (hipStream_t)stream,
+                           partial, out, H, chunk, nsplit);
     return dol_last_error();
 }
 
@@ -885,7 +931,7 @@ extern "C" int dolomite_adamw_step(dolomite_stream_t stream,
 // ===========================================================================
 // Deterministic squared-sum (grad-norm input): fixed-order per-thread
 // strided accumulation + a fixed LDS tree per block -> one fp32 partial per
-// block, folded by dolomite_reduce_partials (fixed loop order). Reading the
+// block, folded by one more fixed tree (sqsum_fold_kernel). Reading the
 // bf16 flat grads directly halves the bytes of the fp32-cast-then-
 // pow(2).sum() path, and the fixed reduction order keeps grad-norm (and so
 // the clipped step) bit-deterministic for checkpoint-resume.
@@ -960,8 +1006,7 @@ extern "C" int dolomite_sqsum(dolomite_stream_t stream, const void* x, int64_t n
         hipLaunchKernelGGL((sqsum_kernel<float>), grid, block, 0, s, (const float*)x, n, partials);
     int err = dol_last_error();
     if (err) return err;
-    // NOT dolomite_reduce_partials: its multi-split path joins with fp32
-    // atomicAdd (order-nondeterministic). One block, fixed tree.
+    // one block, fixed tree (1024 scalars: not worth reduce_partials' two passes)
     hipLaunchKernelGGL((sqsum_fold_kernel), dim3(1), dim3(256), 0, s, partials, out);
     return dol_last_error();
 }

@@ -149,11 +149,13 @@ class FusedRMSNorm(torch.autograd.Function):
                 ),
                 "rmsnorm_bwd",
             )
-            dw32 = torch.zeros(H, dtype=torch.float32, device=s.device)
-            hip.check(
-                hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dw_partial), hip.ptr(dw32), nb, H),
-                "reduce_partials",
-            )
+            # fixed-order reduce (reduce_partials_ref): dw is bitwise reproducible
+            dw32 = torch.empty(H, dtype=torch.float32, device=s.device)
+            with hip.prof("reduce_partials"):
+                hip.check(
+                    hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dw_partial), hip.ptr(dw32), nb, H),
+                    "reduce_partials",
+                )
             dw = dw32.to(weight.dtype)
             dx = dx.view(ctx.shape)
         else:
@@ -167,6 +169,27 @@ class FusedRMSNorm(torch.autograd.Function):
 
 def fused_rmsnorm(x, weight, eps, residual=None):
     return FusedRMSNorm.apply(x, weight, eps, residual)
+
+
+def reduce_partials_ref(partial: torch.Tensor) -> torch.Tensor:
+    """The summation order of dolomite_reduce_partials (definition:
+    include/dolomite_hip.h), restated with sequential fp32 adds on CPU.
+    partial: (nblocks, H) fp32. fp32 adds are IEEE-exact on both sides, so
+    the kernel's result equals this bit for bit."""
+    p = partial.detach().to("cpu", torch.float32)
+    nblocks, H = p.shape
+    nsplit = max(1, min(32, -(-nblocks // 128)))
+    chunk = -(-nblocks // nsplit)
+    out = torch.zeros(H, dtype=torch.float32)
+    for c in range(nsplit):
+        acc = torch.zeros(H, dtype=torch.float32)
+        for i in range(c * chunk, min((c + 1) * chunk, nblocks)):
+            acc = torch.add(acc, p[i])
+        if nsplit == 1:
+            return acc
+        if c * chunk < nblocks:
+            out = torch.add(out, acc)
+    return out
 
 
 # ---------------------------------------------------------------------------
@@ -233,13 +256,14 @@ class FusedLayerNorm(torch.autograd.Function):
                 "layernorm_bwd",
             )
             # dw partials are rows [0, nb), db rows [nb, 2nb) — reduce both
-            # halves separately (out buffers zeroed: atomic join)
-            dw32 = torch.zeros(H, dtype=torch.float32, device=s.device)
-            db32 = torch.zeros(H, dtype=torch.float32, device=s.device)
-            hip.check(hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dwdb), hip.ptr(dw32), nb, H), "rp")
-            hip.check(
-                hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dwdb, nb * H), hip.ptr(db32), nb, H), "rp"
-            )
+            # halves separately, each in the fixed order of reduce_partials_ref
+            dw32 = torch.empty(H, dtype=torch.float32, device=s.device)
+            db32 = torch.empty(H, dtype=torch.float32, device=s.device)
+            with hip.prof("reduce_partials"):
+                hip.check(hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dwdb), hip.ptr(dw32), nb, H), "rp")
+                hip.check(
+                    hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dwdb, nb * H), hip.ptr(db32), nb, H), "rp"
+                )
             dw = dw32.to(weight.dtype)
             db = db32.to(weight.dtype)
             dx = dx.view(ctx.shape)
@@ -320,16 +344,29 @@ class RoPEPackedQKV(torch.autograd.Function):
         cos, sin = ctx.saved_tensors
         lo = ctx.layout
         if dqkv.is_cuda:
+            # The incoming grad may be shared (the caller's own tensor, or a
+            # grad autograd still holds for another consumer), so it is not
+            # rotated in place: q,k go out of place through the kernel, which
+            # leaves the v slots alone, and v (a sliver of the row) is copied.
             dqkv = dqkv.contiguous()
+            T = dqkv.shape[0]
+            out = torch.empty_like(dqkv)
+            if T > 0:
+                # as_strided offsets are absolute in the storage: add each
+                # tensor's own (dqkv may be a slice of a larger buffer)
+                size, stride = (T, lo.Hkv, lo.D), (lo.row_len, lo.kv_hstride, 1)
+                out.as_strided(size, stride, out.storage_offset() + lo.v_off).copy_(
+                    dqkv.as_strided(size, stride, dqkv.storage_offset() + lo.v_off)
+                )
             hip.check(
                 hip.lib().dolomite_rope_qkv(
-                    hip.stream(), hip.ptr(dqkv), hip.ptr(dqkv), hip.ptr(cos), hip.ptr(sin),
-                    dqkv.shape[0], lo.row_len, lo.H, lo.Hkv, lo.D, lo.G,
+                    hip.stream(), hip.ptr(dqkv), hip.ptr(out), hip.ptr(cos), hip.ptr(sin),
+                    T, lo.row_len, lo.H, lo.Hkv, lo.D, lo.G,
                     lo.q_gstride, lo.k_off, lo.kv_hstride, -1, 0, hip.dt(dqkv),
                 ),
                 "rope_qkv bwd",
             )
-            return dqkv, None, None, None
+            return out, None, None, None
         return _rope_cpu(dqkv, cos, sin, lo, inverse=True), None, None, None
 
 
@@ -593,7 +630,7 @@ class FusedCrossEntropy(torch.autograd.Function):
         T, V = logits.shape
         if logits.is_cuda:
             row_stride = logits.stride(0)
-            assert logits.stride(1) == 1
+            assert logits.stride(1) == 1 and (T <= 1 or row_stride >= V), "logits rows must be dense and disjoint"
             row_loss = torch.empty(T, dtype=torch.float32, device=logits.device)
             lse = torch.empty(T, dtype=torch.float32, device=logits.device)
             with hip.prof("ce_fwd"):
@@ -623,12 +660,16 @@ class FusedCrossEntropy(torch.autograd.Function):
         if logits.is_cuda:
             # device-side scale: no host readback of gout/n_valid
             gs_dev = (gout.float() / n_valid.float()).reshape(1).contiguous()
-            dlogits = torch.empty_like(logits)
+            # the kernel reads logits and writes dlogits with ONE row stride:
+            # give dlogits the logits' stride (empty_like of a row-strided
+            # view would be dense, and the kernel would write past its end)
+            row_stride = logits.stride(0)
+            dlogits = torch.empty_strided((T, V), (row_stride, 1), dtype=logits.dtype, device=logits.device)
             with hip.prof("ce_bwd"):
              hip.check(
                 hip.lib().dolomite_ce_bwd(
                     hip.stream(), hip.ptr(logits), hip.ptr(labels), hip.ptr(lse),
-                    hip.ptr(dlogits), hip.ptr(gs_dev), T, V, logits.stride(0),
+                    hip.ptr(dlogits), hip.ptr(gs_dev), T, V, row_stride,
                     ctx.ignore_index, hip.dt(logits),
                 ),
                 "ce_bwd",

@@ -53,7 +53,12 @@ int dolomite_rmsnorm_fwd(dolomite_stream_t stream,
  *         dx in the same pass instead of a separate elementwise add)
  *   dw  = sum_rows(dy * cast_to_dtype(s_hat))        (fp32 accumulation)
  * dw_partial: (nblocks, H) fp32 scratch written by the kernel;
- * dolomite_reduce_partials sums it into dw (H,) fp32.
+ * dolomite_reduce_partials sums it into dw (H,) fp32 in a fixed order, so
+ * dw (and LayerNorm's db) are bitwise reproducible.
+ * Error 9002 (returned before anything is launched): H too wide for one
+ * wave to hold a row in registers — H > 8192 for bf16 with H % 8 == 0,
+ * H > 4096 for fp32 with H % 4 == 0, H > 1024 for any other H. Holds for
+ * all four norm entry points (rmsnorm/layernorm, fwd/bwd).
  * nblocks is returned by dolomite_rmsnorm_bwd_nblocks(T). */
 int dolomite_rmsnorm_bwd_nblocks(int64_t T);
 int dolomite_rmsnorm_bwd(dolomite_stream_t stream,
@@ -74,7 +79,19 @@ int dolomite_layernorm_bwd(dolomite_stream_t stream,
                            void* dx, float* dwdb_partial,
                            const void* dres_in, int64_t T, int64_t H, int dtype);
 
-/* Sum partials: out[h] = sum_i partial[i*H + h]; out fp32 (H,). */
+/* Sum partials: out[h] = sum_i partial[i*H + h]; out fp32 (H,), need not be
+ * zeroed. The summation order is FIXED (no atomics), so the result is
+ * bitwise reproducible run to run:
+ *   nsplit = min(32, ceil(nblocks / 128)),  chunk = ceil(nblocks / nsplit)
+ *   s_c[h] = ((0 + partial[i0,h]) + partial[i0+1,h]) + ...   for rows
+ *            i0 = c*chunk .. min(i0 + chunk, nblocks) - 1, ascending
+ *   out[h] = ((0 + s_0[h]) + s_1[h]) + ... + s_{nsplit-1}[h], ascending c
+ * all in fp32; for nsplit == 1, out = s_0. The Python restatement is
+ * ops/functional.py reduce_partials_ref.
+ * `partial` is SCRATCH despite the const the signature keeps (the C ABI is
+ * unchanged): it must be mutable memory, and for nsplit > 1 the call
+ * overwrites row c*chunk with s_c (the other rows are left as they were).
+ * No other memory is used. */
 int dolomite_reduce_partials(dolomite_stream_t stream,
                              const float* partial, float* out,
                              int64_t nblocks, int64_t H);
@@ -91,7 +108,10 @@ int dolomite_reduce_partials(dolomite_stream_t stream,
  *        (gpt_dolomite/base.py:289-296).
  *   dir: +1 forward rotation, -1 inverse (exact backward, since the table
  *        halves are duplicated: R^T = -R and S commutes with R).
- * out != in allowed (copy-through), in == out allowed (in-place).
+ * in == out: in place. out != in: only the q and k slots of qkv_out are
+ * written; its v slots are NOT copied from qkv_in and keep what they held
+ * (rotate_v_copy is reserved and ignored) — the caller copies v if it needs
+ * a complete row. Error 9003: odd D.
  * ---------------------------------------------------------------------- */
 int dolomite_rope_qkv(dolomite_stream_t stream,
                       const void* qkv_in, void* qkv_out,

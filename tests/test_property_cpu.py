@@ -194,3 +194,105 @@ def test_fused_ce_cpu_matches_torch(T, V, n_ignore):
     ref.backward()
     torch.testing.assert_close(loss, ref, rtol=1e-6, atol=1e-6)
     torch.testing.assert_close(logits.grad, lr.grad, rtol=1e-5, atol=1e-7)
+
+
+# ---------------------------------------------------------------------------
+# The float64 references, bounds and the fixed-order reduce restatement that
+# tests/test_gpu_elementwise_edges.py checks the HIP kernels with
+# (tests/elementwise_refs.py), exercised
+# here against the CPU branches of the same ops (no GPU needed).
+# ---------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("nblocks", [1, 128, 129, 4096, 4100])
+def test_reduce_partials_ref_order(nblocks):
+    """reduce_partials_ref states the order of dolomite_reduce_partials:
+    up to 128 rows it is one ascending sequential sum; beyond, it is the
+    ascending fold of its own per-chunk results; always close to float64."""
+    from dolomite_engine_amd.ops.functional import reduce_partials_ref
+
+    H = 40
+    g = torch.Generator().manual_seed(nblocks)
+    p = torch.randn(nblocks, H, generator=g) * 3.0 + 0.25
+    got = reduce_partials_ref(p)
+    assert got.dtype == torch.float32 and got.shape == (H,)
+    nsplit = max(1, min(32, -(-nblocks // 128)))
+    chunk = -(-nblocks // nsplit)
+
+    def seq(rows):
+        acc = torch.zeros(H)
+        for row in rows:
+            acc = acc + row
+        return acc
+
+    if nsplit == 1:
+        assert torch.equal(got, seq(p))
+    else:
+        sums = [seq(p[c * chunk:(c + 1) * chunk]) for c in range(nsplit)]
+        assert sum(len(p[c * chunk:(c + 1) * chunk]) for c in range(nsplit)) == nblocks
+        assert torch.equal(got, seq(sums))
+        if chunk <= 128:  # a chunk short enough to be single-split is the function itself
+            assert torch.equal(sums[1], reduce_partials_ref(p[chunk:2 * chunk]))
+    p64 = p.double()
+    assert bool(((got.double() - p64.sum(0)).abs() <= (nblocks - 1) * 2.0**-24 * p64.abs().sum(0)).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("TV", [(5, 100), (7, 1001)], ids=str)
+def test_fused_ce_cpu_row_strided_view(TV, dtype):
+    """CPU branch on logits = buf[:, :V] of a wider buffer: loss and
+    gradient inside the float64 bounds of the GPU test, gradient of the
+    logits' shape, buffer untouched."""
+    from dolomite_engine_amd.ops import fused_cross_entropy
+    from tests.elementwise_refs import SENTINEL, _ce_labels, _within, ce_bounds, ce_ref64
+
+    T, V = TV
+    g = torch.Generator().manual_seed(700 + V)
+    logits = (torch.randn(T, V, generator=g) * 2.0 + 0.5).to(dtype)
+    labels = _ce_labels(g, T, V)
+    buf = torch.full((T, V + 24), SENTINEL, dtype=dtype)
+    buf[:, :V] = logits
+    keep = buf.clone()
+    lg = buf[:, :V].detach().requires_grad_(True)
+    assert lg.stride(0) == V + 24
+    loss = fused_cross_entropy(lg, labels)
+    loss.backward()
+    ref = ce_ref64(logits, labels)
+    b = ce_bounds(ref, dtype)
+    assert lg.grad.shape == (T, V)
+    _within("cpu ce loss", loss, ref["loss"], torch.tensor(b["loss"], dtype=torch.float64))
+    _within("cpu ce dlogits", lg.grad, ref["dlogits"], b["dlogits"])
+    assert torch.equal(buf, keep)
+
+
+@pytest.mark.parametrize("fused", [False, True], ids=["plain", "res+ds"])
+@pytest.mark.parametrize("kind", ["rms", "ln"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("shape", [(8195, 64), (37, 100), (5, 1023), (9, 1536), (1, 8)], ids=str)
+def test_norm_cpu_branch_inside_float64_bounds(shape, dtype, kind, fused):
+    """The CPU restatements of the fused norms pass the float64 bounds the
+    GPU kernels are held to (so the bounds admit a correct implementation
+    and reject one that loses a row or a column)."""
+    from dolomite_engine_amd.ops import fused_layernorm, fused_rmsnorm
+    from tests.elementwise_refs import _norm_inputs, check_norm_against_ref, norm_ref64
+
+    T, H = shape
+    inp = _norm_inputs(kind, T, H, dtype, fused, seed=100 + H)
+    x = inp["x"].clone().requires_grad_(True)
+    w = inp["w"].clone().requires_grad_(True)
+    r = inp["res"].clone().requires_grad_(True) if fused else None
+    if kind == "rms":
+        y, s = fused_rmsnorm(x, w, 1e-5, residual=r)
+    else:
+        b = inp["b"].clone().requires_grad_(True)
+        y, s = fused_layernorm(x, w, b, 1e-5, residual=r)
+    if fused:
+        torch.autograd.backward([y, s], [inp["dy"], inp["ds"]])
+        assert torch.equal(r.grad, x.grad)
+    else:
+        y.backward(inp["dy"])
+    got = dict(y=y, dx=x.grad, dw=w.grad)
+    if kind == "ln":
+        got["db"] = b.grad
+    ref = norm_ref64(kind, inp, 1e-5, dtype)
+    check_norm_against_ref("cpu", kind, got, ref, dtype)
