@@ -7,21 +7,31 @@
 // (attention/base.py:72-81) via (t_stride, group_stride) addressing.
 //
 // Design (CDNA4-first):
-//   - MFMA v_mfma_f32_16x16x32_bf16 for QK^T and PV; 64-wide waves.
+//   - MFMA v_mfma_f32_16x16x32_bf16 for both products; 64-wide waves.
 //   - forward: workgroup = 8 waves = 512 threads; q-tile 128 rows (16 per
-//     wave), k-tile 64 keys streamed through LDS as row-major [key][d]
-//     images (stride DPAD+16, conflict-free b128 B-frag reads); the PV
-//     B-fragment comes from the PI23-rowed V image via ds_read_b64_tr_b16.
-//   - online softmax in fp32 VGPRs, m/l carried per row, row reductions as
-//     DPP row_ror rotations (the C-fragment's 16 columns of one row).
-//   - P routed through a per-wave LDS tile to re-shape C-layout -> A-layout;
-//     the PV B-fragment comes from the PI23 V image via depth-3 counted
-//     tr16 ladders.
+//     wave), k-tile 64 keys streamed through LDS as two row-major [key][d]
+//     images in natural row order (stride DPAD+16: the b128 row reads, the
+//     staging writes and the transpose reads are all conflict-free).
+//   - the score tile is computed TRANSPOSED, S^T = K*Q^T (K image row as
+//     the A operand, the wave's Q register fragment as B), so a lane owns
+//     ONE q row: 16 of its 64 scores per tile, the other 48 on the lanes
+//     l^16, l^32, l^48 (see "Swapped-operand score tiles").
+//   - online softmax in fp32 VGPRs with one m / alpha per lane; the row max
+//     crosses the 4 lane groups with v_permlane16_swap + v_permlane32_swap
+//     (VALU, no LDS); the row sum stays a per-lane partial until the
+//     epilogue; the softmax scale is one FMA inside the exponent.
+//   - P never touches LDS: the lane's 16 probabilities pack into the B
+//     operand of O^T = V^T*P^T, whose A operand is a ds_read_b64_tr_b16 of
+//     the V image in the matching (permuted) key order, through a depth-3
+//     counted ladder. O^T leaves as one 8-byte store per lane and 16-wide
+//     head-dim block.
 //   - LSE (H,T) fp32 written for backward; backward recomputes P. dkv
 //     writes per-q-head (T, H, D) fp32 partials (exclusive stores, no
 //     atomics) reduced in fixed order by the finalize kernel —
-//     deterministic gradients; dq accumulates dQ in registers and stores
-//     bf16 straight into the packed dqkv.
+//     deterministic gradients; dq uses the forward's orientation (S^T and
+//     dP^T with the q row on the lane, dS packed in registers into
+//     dQ^T = K^T*dS^T) and stores bf16 straight into the packed dqkv. dkv
+//     contracts over q and still routes P^T / dS^T through LDS strips.
 //   - attention dropout (flash_attn_varlen_func's dropout_p) is fused: the
 //     keep-mask is a pure counter-based hash of (seed, q-head, global q
 //     token, global k token) — see "Attention dropout keep-mask" below and
@@ -40,6 +50,7 @@
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
@@ -61,10 +72,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // and read h delivers fragment elements e = 4h..4h+3.
 //
 // Conflicts (tools_lds_sim.py, validated against SQ_LDS_BANK_CONFLICT):
-// with S=112 the natural row order 2-way conflicts (rows 0 and 8 alias);
-// storing image rows with bits 2 and 3 SWAPPED makes both the tr reads and
-// the b128 row-major B-frag reads conflict-free. All images consumed by tr
-// reads therefore use PI23 row placement (writers and readers alike).
+// with S=112 the natural row order 2-way conflicts for THIS row pattern
+// (rows 0 and 8 alias); storing image rows with bits 2 and 3 SWAPPED makes
+// both the tr reads and the b128 row-major B-frag reads conflict-free. The
+// dkv images, read in this order, use PI23 row placement (writers and
+// readers alike). The fwd / dq ladders read in the permuted key order of
+// "Swapped-operand score tiles" (8 consecutive rows per 32-lane pass), which
+// is conflict-free in natural order and 2-way conflicted under PI23.
 // ---------------------------------------------------------------------------
 #define PI23(q) (((q) & ~12) | ((((q) >> 2) & 1) << 3) | ((((q) >> 3) & 1) << 2))
 
@@ -110,9 +124,10 @@ __device__ __forceinline__ bf16x8 lds_tr16_bfrag(const __bf16* img, int rowbase,
 // counter never drains to 0 inside the loop.
 //
 // Count discipline: the ladder's waits are exact only if no OTHER lgkm op
-// is outstanding, so each region (a) opens with a full drain that names the
-// already-loaded operands (strip A-fragments), and (b) is fenced with
-// sched_barrier(0) so the compiler cannot move its own ds/smem ops inside.
+// is outstanding, so each region (a) opens with nothing in flight — dkv
+// drains its strip writes; in fwd / dq every earlier LDS read has already
+// been consumed by a score MFMA — and (b) is fenced with sched_barrier(0)
+// so the compiler cannot move its own ds/smem ops inside.
 // ---------------------------------------------------------------------------
 
 // Issue one B-fragment's two transpose reads (no wait): OFF = byte offset of
@@ -152,15 +167,6 @@ __device__ __forceinline__ bf16x8 tr16_join8(bf16x4 lo, bf16x4 hi) {
     return out;
 }
 
-// Full drain opening a ladder region; names the strip fragments the region's
-// MFMAs consume so their (compiler-issued) reads are complete and counted out.
-__device__ __forceinline__ void lgkm_drain2x8(bf16x8& a, bf16x8& b) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ void lgkm_drain4x8(bf16x8& a, bf16x8& b, bf16x8& c, bf16x8& d) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-
 // Branchless guarded 16B load. Requires D % 8 == 0 (every head dim on this
 // path): a chunk is then fully inside [0, D) or fully in the pad, so the
 // guard reduces to ONE wave-divergent-free vector load from a clamped
@@ -176,28 +182,6 @@ __device__ __forceinline__ bf16x8 load_bf16x8_guard(const __bf16* p, int d0, int
     for (int e = 0; e < 8; ++e) r[e] = ok ? r[e] : (__bf16)0.f;
     return r;
 }
-
-// 16-lane row reduction (the 16 columns of one C-fragment row live in the
-// 16 lanes of one quarter-wave). DPP row_ror rotations instead of
-// __shfl_xor: hipcc lowers the xor shuffles to ds_bpermute — 32 LDS
-// instructions (plus their lgkm waits) per fwd loop iteration for an
-// issue-bound kernel. row_ror by 8/4/2/1 inside the 16-lane DPP row is
-// pure VALU and reduces the same 16-lane set.
-__device__ __forceinline__ float qwave_reduce_max(float v) {
-    v = fmaxf(v, dpp_ror_f32<8>(v));
-    v = fmaxf(v, dpp_ror_f32<4>(v));
-    v = fmaxf(v, dpp_ror_f32<2>(v));
-    v = fmaxf(v, dpp_ror_f32<1>(v));
-    return v;
-}
-__device__ __forceinline__ float qwave_reduce_sum(float v) {
-    v += dpp_ror_f32<8>(v);
-    v += dpp_ror_f32<4>(v);
-    v += dpp_ror_f32<2>(v);
-    v += dpp_ror_f32<1>(v);
-    return v;
-}
-
 
 // XCD-aware block remap (guide T1): the dispatcher places flat block id b on
 // XCD b%8, so the raw grid (tile, seq, head) spreads one (seq, head)'s tiles
@@ -278,6 +262,66 @@ static inline uint32_t drop_threshold(float p_drop) {
 static inline bool drop_p_valid(float p_drop) { return p_drop >= 0.f && p_drop < 1.f; }
 
 // ===========================================================================
+// Swapped-operand score tiles (fwd, dq): S^T = K*Q^T
+//
+// With the K image row as the MFMA A operand and the wave's Q register
+// fragment as B (the A and B lane maps are symmetric, so the fragment is the
+// one Q*K^T used), the C fragment of key block cb holds, on lane l reg x,
+//   q row  l & 15            key  16*cb + 4*(l>>4) + x.
+// One q row's 64 scores are then 16 registers on each of the 4 lanes
+// {l, l^16, l^32, l^48}: the row statistics are one value per lane, and the
+// 8 values of key blocks (2c, 2c+1) pack, with no lane movement and no LDS,
+// into the B operand of the next product (O^T = V^T*P^T, dQ^T = K^T*dS^T).
+// That fragment's element e on lane group g is key
+//   32c + 16*(e>>2) + 4g + (e&3)                    ("permuted key order"),
+// and the A operand of the next product must contract in the same order:
+// it is a tr16 read of the row-major V (dq: K) image whose per-lane row
+// address is 32c + 16h + 4g + ((l>>2)&3) for read h — fa_tr16_perm_bases.
+// Outputs come out transposed (head-dim 16*dc + 4g + x on the registers,
+// q on l & 15): 4 contiguous bf16 per lane and block, one 8-byte store.
+// ===========================================================================
+
+// K/V image geometry shared by the fwd and dq kernels and their launchers:
+// two 64-row images of stride S and, with dropout, the staged tile's 64
+// keep-mask column words behind them — nothing else in dynamic LDS.
+template <int DPAD>
+struct FaKvLds {
+    static constexpr int S = DPAD + 16;
+    static constexpr size_t image_bytes = (size_t)2 * 64 * S * sizeof(__bf16);  // multiple of 256
+    static constexpr size_t bytes(bool dropout) {
+        return image_bytes + (dropout ? 64 * sizeof(uint32_t) : 0);
+    }
+};
+
+// lane base addresses (reads h = 0, 1) of the permuted-key tr16 ladder over
+// a natural-row image of stride S
+__device__ __forceinline__ void fa_tr16_perm_bases(const __bf16* img, int S, int lane,
+                                                   unsigned& a0, unsigned& a1) {
+    const int row = (lane >> 4) * 4 + ((lane >> 2) & 3);
+    const int cc = (lane & 3) * 4;
+    a0 = (unsigned)(size_t)(img + row * S + cc);
+    a1 = (unsigned)(size_t)(img + (16 + row) * S + cc);
+}
+
+// Reductions over the 4 lanes {l, l^16, l^32, l^48} that share one q row:
+// v_permlane16_swap exchanges the odd 16-lane rows of its first operand with
+// the even rows of its second, v_permlane32_swap the upper half-wave of the
+// first with the lower half of the second. With both operands the same
+// value each returned pair holds (own, partner) on every lane. Pure VALU.
+__device__ __forceinline__ float qgroup_reduce_max(float v) {
+    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+__device__ __forceinline__ float qgroup_reduce_sum(float v) {
+    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
+
+// ===========================================================================
 // Forward
 // ===========================================================================
 
@@ -290,17 +334,12 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     int64_t o_ts, int64_t T_total, float scale,
     uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
     constexpr int KCH = DPAD / 32;   // contraction chunks for QK^T
-    constexpr int DCH = DPAD / 16;   // output col blocks for PV
-    // Strides chosen with tools_lds_sim.py (exact gfx950 bank model):
-    //   row-major K image: stride DPAD+16 makes every b128 B-frag read
-    //     conflict-free (the b128 lane groups mix two lg half-rows offset by
-    //     4 dwords; +8 padding left them 2-way conflicted);
-    //   transposed V image: stride 96 + block swizzle (col>>3)^(3*(row>>3)&7)
-    //     -> conflict-free b128 reads;
-    //   P strips: stride 72 (b16 writes conflict-free; reads 2-way — the
-    //     reverse trade costs more write cycles than it saves).
-    constexpr int SK = DPAD + 16;    // K/V LDS row stride (elems)
-    constexpr int SV = 64 + 8;       // P strip row stride
+    constexpr int DCH = DPAD / 16;   // output row blocks of O^T
+    // Stride chosen with tools_lds_sim.py (exact gfx950 bank model): DPAD+16
+    // makes the b128 row reads of the K image, the b128 staging writes and
+    // the key-permuted tr16 reads of the V image (8 consecutive rows per
+    // 32-lane pass) all conflict-free with rows in natural order.
+    constexpr int SK = FaKvLds<DPAD>::S;   // K/V LDS row stride (elems)
 
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
@@ -334,19 +373,18 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     //       failures across runs; see git history for the full variant).
     // At 2 workgroups/CU the co-resident workgroup already hides staging
     // latency, so the single-buffer two-barrier schedule stays.
-    constexpr int NBUF = 1;
-    extern __shared__ char smem_raw[];
-    __bf16* Klds = (__bf16*)smem_raw;              // [NBUF][64][SK]
-    __bf16* Vlds = Klds + NBUF * 64 * SK;          // [NBUF][64 key][SK] (PI23 rows)
-    __bf16* Plds = Vlds + NBUF * 64 * SK;          // [8 waves][16][SV]
-    __bf16* Pw = Plds + wave * 16 * SV;
-    // V is stored row-major (coalesced staging) and consumed as the PV
-    // B-fragment via ds_read_b64_tr_b16 — no transposed image, no scatter.
+    extern __shared__ char smem_raw[];             // FaKvLds<DPAD>::bytes(DROPOUT)
+    __bf16* Klds = (__bf16*)smem_raw;              // [64 key][SK]
+    __bf16* Vlds = Klds + 64 * SK;                 // [64 key][SK]
+    uint32_t* Cw = (uint32_t*)(Vlds + 64 * SK);    // [64 key] column words (DROPOUT only)
+    // V is stored row-major (coalesced staging) and consumed as the V^T
+    // A-fragment via ds_read_b64_tr_b16 — no transposed image, no scatter.
 
     const int kvh = h / G;
     const int64_t q_hoff = (int64_t)(h / G) * q_gs + (int64_t)(h % G) * D;
 
-    // --- load this wave's Q fragments (A-layout: i = lr, k = lg*8+e) ---
+    // --- load this wave's Q fragments (B-layout of Q^T: j = lr -> q row,
+    // k = lg*8+e -> head dim) ---
     const int qrow = qs + wave * 16 + lr;
     const bool qvalid = qrow < L;
     bf16x8 qf[KCH];
@@ -357,31 +395,31 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
         qf[kc] = load_bf16x8_guard(p, d0, D, qvalid);
     }
 
-    float m_run[4], l_run[4];
-    f32x4 o_acc[DCH];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { m_run[r] = -INFINITY; l_run[r] = 0.f; }
+    // One q row (qrow) per lane: a single running max and alpha. m_run is
+    // identical on the row's 4 lanes; l_run is this lane's PARTIAL row sum
+    // (its 16 keys per tile) — alpha is shared, so the partials rescale
+    // alike and are joined once, in the epilogue.
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x4 o_acc[DCH];              // O^T: d = dc*16 + lg*4 + x, q = lr
 #pragma unroll
     for (int dc = 0; dc < DCH; ++dc) o_acc[dc] = {0.f, 0.f, 0.f, 0.f};
 
-    // dropout: this lane's 4 q rows are fixed for the kernel, so their row
-    // words are hoisted; column words are per key tile (compute_tile)
-    uint32_t drop_rw[4];
+    // dropout: the lane's q row is fixed for the kernel, so its row word is
+    // hoisted. A lane's 16 scores per tile are 16 different keys, so the
+    // tile's 64 column words are mixed ONCE per workgroup (wave 0, one key
+    // per lane, next to the staging) and read back as four broadcast b128
+    // loads — 16 mixes per lane and tile would cost more than the mask test
+    uint32_t drop_rw = 0;
     uint32_t drop_hw = 0;
     if constexpr (DROPOUT) {
         drop_hw = drop_head_word(seed_hi, (uint32_t)h);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            drop_rw[r] = drop_row_word(seed_lo, (uint32_t)(s0 + qs + wave * 16 + lg * 4 + r));
+        drop_rw = drop_row_word(seed_lo, (uint32_t)(s0 + qrow));
     }
 
-    // lane base addresses for the PV tr16 ladder (PI23 row placement; the
-    // per-step (rowbase, d0) displacement goes in the ds_read immediate)
-    const int tr_jj = (lane >> 2) & 3;
-    const int tr_g8 = (lane >> 4) * 8;
-    const int tr_cc = (lane & 3) * 4;
-    const unsigned aV0 = (unsigned)(size_t)(Vlds + PI23(tr_g8 + tr_jj) * SK + tr_cc);
-    const unsigned aV1 = (unsigned)(size_t)(Vlds + PI23(tr_g8 + 4 + tr_jj) * SK + tr_cc);
+    // lane base addresses for the PV tr16 ladder (permuted key order; the
+    // per-step (chunk, d0) displacement goes in the ds_read immediate)
+    unsigned aV0, aV1;
+    fa_tr16_perm_bases(Vlds, SK, lane, aV0, aV1);
 
     const int kend = min(L, qs + 128);
     const int ntiles = (kend + 63) / 64;
@@ -392,7 +430,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
             int d0 = D + (pidx % ((DPAD - D) / 8)) * 8;
             bf16x8 z = {};
             *(bf16x8*)&Klds[key * SK + d0] = z;
-            *(bf16x8*)&Vlds[PI23(key) * SK + d0] = z;
+            *(bf16x8*)&Vlds[key * SK + d0] = z;
         }
     }
 
@@ -408,7 +446,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
         st_koff[j] = (int)(key * k_ts + kvh * k_hs) + d0;   // fits 32 bits
         st_voff[j] = (int)(key * v_ts + kvh * v_hs) + d0;
         st_klds[j] = key * SK + d0;
-        st_vlds[j] = PI23(key) * SK + d0;
+        st_vlds[j] = key * SK + d0;
     }
 
     // T5 static priority: the later-dispatched half of an 8-wave workgroup
@@ -417,7 +455,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
 
     constexpr int PIECES = 64 * DPAD / 8;  // 8-elem staging pieces
 
-    // direct cooperative staging (prologue and the NBUF==1 path)
+    // direct cooperative staging
     auto stage_direct = [&](int ks_, __bf16* Kw, __bf16* Vw) {
         if (ks_ + 64 <= kend) {
             const int64_t disp = (int64_t)(s0 + ks_);
@@ -436,13 +474,19 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
                 const __bf16* kp = k + (int64_t)(s0 + (kv_valid ? ks_ + key : 0)) * k_ts + (int64_t)kvh * k_hs + d0;
                 *(bf16x8*)&Kw[key * SK + d0] = load_bf16x8_guard(kp, d0, D, kv_valid);
                 const __bf16* vp = v + (int64_t)(s0 + (kv_valid ? ks_ + key : 0)) * v_ts + (int64_t)kvh * v_hs + d0;
-                *(bf16x8*)&Vw[PI23(key) * SK + d0] = load_bf16x8_guard(vp, d0, D, kv_valid);
+                *(bf16x8*)&Vw[key * SK + d0] = load_bf16x8_guard(vp, d0, D, kv_valid);
             }
         }
     };
 
+    // softmax scale folded into the exponent as one FMA per score; the row
+    // max is taken on the raw scores, which orders them alike for scale > 0
+    // (the dispatcher rejects anything else)
+    const float scale2 = scale * DOL_LOG2E;  // exp2-domain scores
+
     auto compute_tile = [&](const __bf16* Kb, unsigned aV0c, unsigned aV1c, int ks) {
-        // --- QK^T: 4 key-blocks of 16, accumulate over KCH chunks ---
+        // --- S^T = K*Q^T: 4 key-blocks of 16, accumulate over KCH chunks;
+        // sc[cb][x] is (q = qrow, key = ks + 16*cb + 4*lg + x) ---
         f32x4 sc[4];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
@@ -450,75 +494,69 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
 #pragma unroll
             for (int kc = 0; kc < KCH; ++kc) {
                 bf16x8 kf = *(const bf16x8*)&Kb[(cb * 16 + lr) * SK + kc * 32 + lg * 8];
-                sc[cb] = MFMA16(qf[kc], kf, sc[cb]);
+                sc[cb] = MFMA16(kf, qf[kc], sc[cb]);
             }
         }
 
-        // --- mask + online softmax (fp32), streamed per C-row: the row's
-        // 4 scores live in 4 registers and P goes straight to the LDS strip
-        // (keeps the per-tile live set small for the 128-VGPR cap).
+        // --- mask + online softmax (fp32), one q row per lane.
         // Wave-uniform mask split: full tiles skip the per-element compare
-        // chain entirely (the kernel is issue-bound); the -INF guards for
-        // the FIRST tile's running max stay in both branches. ---
-        const float scale2 = scale * DOL_LOG2E;  // exp2-domain scores
-        // One body, two cheap reductions of per-element work:
-        //  - the mask-compare chain runs only on edge tiles (wave-uniform
-        //    branch; a full dual-body split cost fwd 32 VGPRs + spills);
-        //  - the -INFINITY select guards are gone: v_exp_f32(-inf) is
-        //    exactly +0, and mnew is never -inf after the fully-masked-row
-        //    force, so exp2f does the zeroing for free.
+        // chain entirely (the kernel is issue-bound). No -INFINITY select
+        // guards: v_exp_f32(-inf) is exactly +0, and mnew is never -inf
+        // after the fully-masked-row force, so exp2f does the zeroing. ---
         const bool edge_tile =
             !((ks + 63 <= qs + wave * 16) && (ks + 64 <= kend) && (qs + wave * 16 + 16 <= L));
-        // dropout touches ONLY the bf16 P written to the strip: the online
-        // softmax (rsum / l_run / m_run, hence lse) sees the undropped e
-        uint32_t drop_cw[4];
-        if constexpr (DROPOUT) {
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-                drop_cw[cb] = drop_col_word(drop_hw, (uint32_t)(s0 + ks + cb * 16 + lr));
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float pv[4];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) pv[cb] = sc[cb][r] * scale2;
-            if (__builtin_amdgcn_readfirstlane(edge_tile ? 1 : 0)) {
-                const int qpos = qs + wave * 16 + lg * 4 + r;
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) {
-                    const int kpos = ks + cb * 16 + lr;
-                    if (kpos > qpos || kpos >= kend || qpos >= L) pv[cb] = -INFINITY;
-                }
-            }
-            float rowmax = fmaxf(fmaxf(pv[0], pv[1]), fmaxf(pv[2], pv[3]));
-            rowmax = qwave_reduce_max(rowmax);
-            float mnew = fmaxf(m_run[r], rowmax);
-            if (mnew == -INFINITY) mnew = 0.f;  // fully-masked row guard
-            float alpha = exp2f(m_run[r] - mnew);
-            float rsum = 0.f;
+        if (__builtin_amdgcn_readfirstlane(edge_tile ? 1 : 0)) {
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
-                float e = exp2f(pv[cb] - mnew);
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    const int kpos = ks + cb * 16 + lg * 4 + x;
+                    if (kpos > qrow || kpos >= kend || qrow >= L) sc[cb][x] = -INFINITY;
+                }
+            }
+        }
+        float mx[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+            mx[cb] = fmaxf(fmaxf(sc[cb][0], sc[cb][1]), fmaxf(sc[cb][2], sc[cb][3]));
+        const float rowmax = qgroup_reduce_max(fmaxf(fmaxf(mx[0], mx[1]), fmaxf(mx[2], mx[3])));
+        float mnew = fmaxf(m_run, rowmax * scale2);
+        if (mnew == -INFINITY) mnew = 0.f;  // fully-masked row guard
+        const float alpha = exp2f(m_run - mnew);
+        m_run = mnew;
+
+        // dropout touches ONLY the packed bf16 P: the online softmax
+        // (rsum / l_run / m_run, hence lse) sees the undropped e.
+        // pf[c] element e is key 32c + 16*(e>>2) + 4*lg + (e&3) — the order
+        // the V^T ladder below contracts in.
+        bf16x8 pf[2];
+        float rsum = 0.f;
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            u32x4 cw = {};
+            if constexpr (DROPOUT) cw = *(const u32x4*)&Cw[cb * 16 + lg * 4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const float e = exp2f(fmaf(sc[cb][x], scale2, -mnew));
                 float ek = e;
-                if constexpr (DROPOUT)
-                    ek = drop_keep_words(drop_rw[r], drop_cw[cb], drop_thr) ? e : 0.f;
-                Pw[(lg * 4 + r) * SV + cb * 16 + lr] = (__bf16)ek;
+                if constexpr (DROPOUT) ek = drop_keep_words(drop_rw, cw[x], drop_thr) ? e : 0.f;
+                pf[cb >> 1][(cb & 1) * 4 + x] = (__bf16)ek;
                 rsum += e;
             }
-            rsum = qwave_reduce_sum(rsum);
-            l_run[r] = l_run[r] * alpha + rsum;
-            m_run[r] = mnew;
+        }
+        l_run = l_run * alpha + rsum;
+        // exact skip: alpha is 1.0f wherever the running max did not move
+        if (!__all(alpha == 1.0f)) {
 #pragma unroll
-            for (int dc = 0; dc < DCH; ++dc) o_acc[dc][r] *= alpha;
+            for (int dc = 0; dc < DCH; ++dc) o_acc[dc] *= alpha;
         }
 
-        // --- PV: A = P (this wave's rows), B via the pipelined tr16 ladder
-        // over the row-major PI23 V image (issue frag i+1, counted-wait
-        // frag i, MFMA — LDS latency hides under the matrix pipe) ---
+        // --- O^T += V^T*P^T: B = packed P (registers), A via the pipelined
+        // tr16 ladder over the row-major V image (issue frag i+1,
+        // counted-wait frag i, MFMA — LDS latency hides under the matrix
+        // pipe). The K reads above were consumed by the score MFMAs, so no
+        // LDS op is outstanding when the ladder opens. ---
         {
-            bf16x8 pf0 = *(const bf16x8*)&Pw[lr * SV + lg * 8];
-            bf16x8 pf1 = *(const bf16x8*)&Pw[lr * SV + 32 + lg * 8];
-            lgkm_drain2x8(pf0, pf1);
             __builtin_amdgcn_sched_barrier(0);
             // depth-3 pipeline: two fragments stay in flight — ONE MFMA
             // (~17 cyc) does not cover the ~50-cycle LDS read latency that
@@ -538,7 +576,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
         } else {                                                                                        \
             lgkm_wait2<0>(vlo[(i) % 3], vhi[(i) % 3]);                                                  \
         }                                                                                               \
-        o_acc[dc_] = MFMA16(kc2_ ? pf1 : pf0, tr16_join8(vlo[(i) % 3], vhi[(i) % 3]), o_acc[dc_]);      \
+        o_acc[dc_] = MFMA16(tr16_join8(vlo[(i) % 3], vhi[(i) % 3]), pf[kc2_], o_acc[dc_]);              \
     }
             FWD_PV_STEP(0) FWD_PV_STEP(1) FWD_PV_STEP(2) FWD_PV_STEP(3)
             FWD_PV_STEP(4) FWD_PV_STEP(5) FWD_PV_STEP(6) FWD_PV_STEP(7)
@@ -549,103 +587,33 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
         }
     };
 
-    if constexpr (NBUF == 2) {
-        // ---- LDS-DMA staging setup ----
-        // Chunk = one buffer_load_dwordx4..lds instruction: 64 lanes x 16 B
-        // of contiguous LDS. Per tensor image: 64*SK*2/1024 chunks; this
-        // wave owns chunks c = wave, wave+8, ... across K then V.
-        constexpr int CH = (64 * SK * 2) / 1024;   // chunks per image (SK%8==0)
-        constexpr int NC = (2 * CH + 7) / 8;       // chunks this wave may own
-        // Per-sequence, per-kv-head buffer descriptors: OOB voffsets
-        // (key >= L, or MFMA pad columns sent out of range) read as zero.
-        auto rsrcK = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(k + (int64_t)s0 * k_ts + (int64_t)kvh * k_hs), 0,
-            (unsigned)(((int64_t)(L - 1) * k_ts + D) * 2), 0);
-        auto rsrcV = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(v + (int64_t)s0 * v_ts + (int64_t)kvh * v_hs), 0,
-            (unsigned)(((int64_t)(L - 1) * v_ts + D) * 2), 0);
-        // Loop-invariant per-lane voffsets (bytes) for key tile 0; per tile
-        // add ks*stride*2. Pad columns get 0x40000000 (stays OOB after the
-        // per-tile add — tensors on this path are < 1 GiB).
-        unsigned choff[NC];
-        bool ch_is_v[NC];
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            int c = wave + i * 8;
-            bool isv = c >= CH;
-            int cc = isv ? c - CH : c;
-            int e0 = cc * 512 + lane * 8;
-            int row = e0 / SK;
-            int col = e0 % SK;
-            int key = isv ? PI23(row) : row;   // V image rows are PI23-placed
-            int64_t ts = isv ? v_ts : k_ts;
-            unsigned off = (unsigned)((key * ts + col) * 2);
-            if (col >= D || c >= 2 * CH) off = 0x40000000u;
-            choff[i] = off;
-            ch_is_v[i] = isv;
+    for (int kt = 0; kt < ntiles; ++kt) {
+        stage_direct(kt * 64, Klds, Vlds);
+        if constexpr (DROPOUT) {
+            if (__builtin_amdgcn_readfirstlane(threadIdx.x) < 64)
+                Cw[lane] = drop_col_word(drop_hw, (uint32_t)(s0 + kt * 64 + lane));
         }
-        const unsigned kstep2 = (unsigned)(k_ts * 2) * 64u;  // voffset delta per 64-key tile
-        const unsigned vstep2 = (unsigned)(v_ts * 2) * 64u;
-
-        auto stage_dma = [&](int kt_, int buf_) {
-            __bf16* Kb = Klds + buf_ * 64 * SK;
-            __bf16* Vb = Vlds + buf_ * 64 * SK;
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-                int c = wave + i * 8;
-                if (c >= 2 * CH) break;
-                bool isv = ch_is_v[i];
-                int cc = isv ? c - CH : c;
-                char* ldsp = (char*)(isv ? Vb : Kb) + cc * 1024;
-                unsigned vo = choff[i] + (unsigned)kt_ * (isv ? vstep2 : kstep2);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                    isv ? rsrcV : rsrcK,
-                    (__attribute__((address_space(3))) void*)ldsp, 16, vo, 0, 0, 0);
-            }
-        };
-
-        stage_dma(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        for (int kt = 0; kt < ntiles; ++kt) {
-            const int cur = kt & 1;
-            if (kt + 1 < ntiles) stage_dma(kt + 1, cur ^ 1);  // in flight under compute
-            compute_tile(Klds + cur * 64 * SK,
-                         aV0 + (unsigned)(cur * 64 * SK * 2),
-                         aV1 + (unsigned)(cur * 64 * SK * 2), kt * 64);
-            // the DMA into buf cur^1 must land before the next iteration
-            // reads it; the barrier then publishes it workgroup-wide
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-    } else {
-        for (int kt = 0; kt < ntiles; ++kt) {
-            stage_direct(kt * 64, Klds, Vlds);
-            __syncthreads();
-            compute_tile(Klds, aV0, aV1, kt * 64);
-            __syncthreads();  // K/V LDS reused next tile
-        }
+        compute_tile(Klds, aV0, aV1, kt * 64);
+        __syncthreads();  // K/V LDS reused next tile
     }
 
-    // --- epilogue: normalize, store O and LSE ---
-    float inv_l[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        inv_l[r] = (l_run[r] > 0.f) ? 1.f / l_run[r] : 0.f;
-        if constexpr (DROPOUT) inv_l[r] *= drop_rp;  // kept P scaled by 1/(1-p)
-        const int qpos = qs + wave * 16 + lg * 4 + r;
-        if (lr == 0 && qpos < L)
-            lse[(int64_t)h * T_total + s0 + qpos] = (m_run[r] + log2f(l_run[r])) * DOL_LN2;
-    }
+    // --- epilogue: join the row's 4 partial sums, normalize, store O^T
+    // (4 contiguous head-dim elements per lane and block) and LSE ---
+    const float l_row = qgroup_reduce_sum(l_run);
+    float inv_l = (l_row > 0.f) ? 1.f / l_row : 0.f;
+    if constexpr (DROPOUT) inv_l *= drop_rp;  // kept P scaled by 1/(1-p)
+    if (lg == 0 && qvalid)
+        lse[(int64_t)h * T_total + s0 + qrow] = (m_run + log2f(l_row)) * DOL_LN2;
+    // D % 8 == 0 on this path: a 4-wide group is all inside D or all pad
+    __bf16* orow = o + (int64_t)(s0 + (qvalid ? qrow : 0)) * o_ts + (int64_t)h * D;
 #pragma unroll
     for (int dc = 0; dc < DCH; ++dc) {
+        const int d0 = dc * 16 + lg * 4;
+        bf16x4 ov;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int qpos = qs + wave * 16 + lg * 4 + r;
-            const int d = dc * 16 + lr;
-            if (qpos < L && d < D)
-                o[(int64_t)(s0 + qpos) * o_ts + (int64_t)h * D + d] = (__bf16)(o_acc[dc][r] * inv_l[r]);
-        }
+        for (int x = 0; x < 4; ++x) ov[x] = (__bf16)(o_acc[dc][x] * inv_l);
+        if (qvalid && d0 < D) *(bf16x4*)&orow[d0] = ov;
     }
 }
 
@@ -657,8 +625,7 @@ static int launch_fa_fwd(hipStream_t stream, const __bf16* q, const __bf16* k, c
                          int64_t v_ts, int64_t v_hs, int max_tiles, float scale,
                          float p_drop, uint64_t seed) {
     dim3 grid(max_tiles, batch, H), block(512);
-    size_t shmem = ((size_t)(DPAD <= 96 ? 2 : 1) * 64 * (DPAD + 16) * 2 + 8 * 16 * 72) * sizeof(__bf16);
-    hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT>), grid, block, shmem, stream,
+    hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT>), grid, block, FaKvLds<DPAD>::bytes(DROPOUT), stream,
                        q, k, v, o, lse, cu, H, Hkv, D, G,
                        q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, (int64_t)H * D, T, scale,
                        (uint32_t)seed, (uint32_t)(seed >> 32), drop_threshold(p_drop),
@@ -679,6 +646,7 @@ static int fa_varlen_fwd_dispatch(dolomite_stream_t stream,
                                   float scale, int dtype, float p_drop, uint64_t seed) {
     if (dtype != DOLOMITE_BF16) return 9010;  // bf16 only (north-star dtype)
     if (D > 128) return 9011;
+    if (!(scale > 0.f)) return 9015;  // the row max is taken before scaling
     // grid.x = tiles of the longest sequence; shorter sequences' surplus
     // workgroups exit on the cu_seqlens check.
     int max_tiles = (max_seqlen + 127) / 128;
@@ -835,11 +803,13 @@ extern "C" int dolomite_fa_bwd_preprocess(dolomite_stream_t stream,
 // Backward is split FA2-style into two kernels (each recomputes P from
 // q/k/lse — cheaper than the atomics+barriers a fused version needs):
 //   fa_bwd_dkv_kernel : grid (kv-tile, seq, q-head); dK/dV accumulate in
-//     registers over the q-tile loop, joined into fp32 buffers by one atomic
-//     pass per workgroup (G q-head contributors per kv strip).
-//   fa_bwd_dq_kernel  : grid (q-tile, seq, q-head); dQ accumulates in
+//     registers over the q-tile loop and are stored once into per-q-head
+//     fp32 partials (G q-head contributors per kv strip, reduced in fixed
+//     order by fa_grad_finalize).
+//   fa_bwd_dq_kernel  : grid (q-tile, seq, q-head); dQ^T accumulates in
 //     registers over the kv-tile loop — no atomics at all — and is stored
-//     once. K^T is the only LDS image (swizzled), staged per kv tile.
+//     once. Row-major K and V images, staged per kv tile; dS stays in
+//     registers (see "Swapped-operand score tiles").
 
 // dkv round-2 structure: NO transposed LDS images. The Q/dO images are
 // stored row-major with PI23 row placement only, read two ways:
@@ -1177,7 +1147,6 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
     constexpr int KCH = DPAD / 32;
     constexpr int DCH = DPAD / 16;
-    constexpr int ST = 64 + 8;                 // strip stride
 
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
@@ -1197,27 +1166,26 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     const int lr = lane & 15;
     const int lg = lane >> 4;
 
-    // Round-2: the swizzled K^T image is gone — the dQ+=dS*K B-fragments
-    // come from the PI23-rowed row-major K image via the tr16 ladder, like
-    // dkv. Saves DPAD*96 LDS elements and the per-piece scatter writes.
-    constexpr int SQ = DPAD + 16;              // image stride
-    extern __shared__ char smem_raw[];
-    __bf16* Klds = (__bf16*)smem_raw;          // [64 key][SQ] (PI23 rows)
-    __bf16* Vlds = Klds + 64 * SQ;             // [64 key][SQ] (natural rows)
-    __bf16* dSl = Vlds + 64 * SQ;              // [8 waves][16 q][ST] (dS strips)
-    __bf16* dSw = dSl + wave * 16 * ST;
+    // Same orientation as the forward (see "Swapped-operand score tiles"):
+    // S^T and dP^T put the q row on the lane, dS^T packs in registers into
+    // the B operand of dQ^T = K^T*dS^T, and the K^T A-fragments come from
+    // the row-major K image via the permuted-key tr16 ladder. Both images
+    // keep natural row order (conflict-free for the b128 row reads, the
+    // staging writes and the tr16 reads at stride DPAD+16).
+    constexpr int SQ = FaKvLds<DPAD>::S;       // image stride
+    extern __shared__ char smem_raw[];         // FaKvLds<DPAD>::bytes(DROPOUT)
+    __bf16* Klds = (__bf16*)smem_raw;          // [64 key][SQ]
+    __bf16* Vlds = Klds + 64 * SQ;             // [64 key][SQ]
+    uint32_t* Cw = (uint32_t*)(Vlds + 64 * SQ);  // [64 key] column words (DROPOUT only)
 
     const int64_t q_hoff = (int64_t)(h / G) * q_gs + (int64_t)(h % G) * D;
     const int64_t do_hoff = (int64_t)h * D;
 
     // lane base addresses for the dQ tr16 ladder over Klds
-    const int tr_jj = (lane >> 2) & 3;
-    const int tr_g8 = (lane >> 4) * 8;
-    const int tr_cc = (lane & 3) * 4;
-    const unsigned aK0 = (unsigned)(size_t)(Klds + PI23(tr_g8 + tr_jj) * SQ + tr_cc);
-    const unsigned aK1 = (unsigned)(size_t)(Klds + PI23(tr_g8 + 4 + tr_jj) * SQ + tr_cc);
+    unsigned aK0, aK1;
+    fa_tr16_perm_bases(Klds, SQ, lane, aK0, aK1);
 
-    // this wave's Q and dO fragments (A-layout: i = lr -> q row)
+    // this wave's Q and dO fragments (B-layout of Q^T/dO^T: j = lr -> q row)
     const int qrow = qs + wave * 16 + lr;
     const bool qvalid = qrow < L;
     bf16x8 qfr[KCH], dfr[KCH];
@@ -1230,28 +1198,23 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
         dfr[kc] = load_bf16x8_guard(dp, d0, D, qvalid);
     }
 
-    float lsev[4], delv[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int qp_ = qs + wave * 16 + lg * 4 + r;
-        bool ok = qp_ < L;
-        lsev[r] = ok ? lse[(int64_t)h * T_total + s0 + qp_] * DOL_LOG2E : 0.f;
-        delv[r] = ok ? delta[(int64_t)h * T_total + s0 + qp_] : 0.f;
-    }
+    // one q row per lane: one lse and one delta
+    const float lsev = qvalid ? lse[(int64_t)h * T_total + s0 + qrow] * DOL_LOG2E : 0.f;
+    const float delv = qvalid ? delta[(int64_t)h * T_total + s0 + qrow] : 0.f;
+    const float scale2 = scale * DOL_LOG2E;
 
-    f32x4 dq[DCH];
+    f32x4 dq[DCH];                 // dQ^T: d = dc*16 + lg*4 + x, q = lr
 #pragma unroll
     for (int dc = 0; dc < DCH; ++dc) dq[dc] = {0.f, 0.f, 0.f, 0.f};
 
-    // dropout: same dS formula as dkv with the fwd-style lane mapping (4 q
-    // rows fixed per lane -> hoisted row words; column words per key block)
-    uint32_t drop_rw[4];
+    // dropout: same dS formula as dkv with the fwd lane mapping (the lane's
+    // q row is fixed -> hoisted row word; the tile's 64 column words are
+    // mixed once per workgroup into Cw, see the forward)
+    uint32_t drop_rw = 0;
     uint32_t drop_hw = 0;
     if constexpr (DROPOUT) {
         drop_hw = drop_head_word(seed_hi, (uint32_t)h);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            drop_rw[r] = drop_row_word(seed_lo, (uint32_t)(s0 + qs + wave * 16 + lg * 4 + r));
+        drop_rw = drop_row_word(seed_lo, (uint32_t)(s0 + qrow));
     }
 
     if (D < DPAD) {  // pad columns zeroed once (see dkv note)
@@ -1259,7 +1222,7 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
             int key = pidx / ((DPAD - D) / 8);
             int d0 = D + (pidx % ((DPAD - D) / 8)) * 8;
             bf16x8 z = {};
-            *(bf16x8*)&Klds[PI23(key) * SQ + d0] = z;
+            *(bf16x8*)&Klds[key * SQ + d0] = z;
             *(bf16x8*)&Vlds[key * SQ + d0] = z;
         }
     }
@@ -1275,7 +1238,7 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
         int d0 = (pp % (D / 8)) * 8;
         st_koff[j] = (int)(key * k_ts + kvh * k_hs) + d0;   // fits 32 bits
         st_voff[j] = (int)(key * v_ts + kvh * v_hs) + d0;
-        st_klds[j] = PI23(key) * SQ + d0;
+        st_klds[j] = key * SQ + d0;
         st_vlds[j] = key * SQ + d0;
     }
 
@@ -1288,7 +1251,7 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     for (int kt = 0; kt < nkt; ++kt) {
         const int ks = kt * 64;
         __syncthreads();  // previous tile's image reads done
-        // stage row-major K (PI23 rows) + V images, cooperative
+        // stage row-major K + V images, cooperative
         {
             const int pieces = 64 * DPAD / 8;
             if (ks + 64 <= kend_total) {
@@ -1306,18 +1269,26 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
                     int d0 = (pidx % (DPAD / 8)) * 8;
                     bool valid = (ks + key) < kend_total;
                     const __bf16* kp = k + (int64_t)(s0 + (valid ? ks + key : 0)) * k_ts + (int64_t)kvh * k_hs + d0;
-                    *(bf16x8*)&Klds[PI23(key) * SQ + d0] = load_bf16x8_guard(kp, d0, D, valid);
+                    *(bf16x8*)&Klds[key * SQ + d0] = load_bf16x8_guard(kp, d0, D, valid);
                     const __bf16* vp = v + (int64_t)(s0 + (valid ? ks + key : 0)) * v_ts + (int64_t)kvh * v_hs + d0;
                     *(bf16x8*)&Vlds[key * SQ + d0] = load_bf16x8_guard(vp, d0, D, valid);
                 }
             }
+            if constexpr (DROPOUT) {
+                if (__builtin_amdgcn_readfirstlane(threadIdx.x) < 64)
+                    Cw[lane] = drop_col_word(drop_hw, (uint32_t)(s0 + ks + lane));
+            }
         }
         __syncthreads();
 
-        // Per key-column block: S = Q*K^T and dP = dO*V^T MFMAs, then that
-        // block's dS straight into the wave's strip (one C-pair live).
+        // Per key block: S^T = K*Q^T and dP^T = V*dO^T MFMAs (element x is
+        // q = qrow, key = ks + 16*cb + 4*lg + x), then that block's dS
+        // packed into half of its 32-key chunk's fragment — one C-pair live.
+        // dsf[c] element e is key 32c + 16*(e>>2) + 4*lg + (e&3), the order
+        // the K^T ladder below contracts in.
         // Wave-uniform mask split (see dkv note).
         const bool full_tile = (ks + 64 <= qs + wave * 16 + 1) && (ks + 64 <= kend_total) && (qs + wave * 16 + 16 <= L);
+        bf16x8 dsf[2];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
             f32x4 sc = {0.f, 0.f, 0.f, 0.f};
@@ -1325,44 +1296,41 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
 #pragma unroll
             for (int kc = 0; kc < KCH; ++kc) {
                 int d0 = kc * 32 + lg * 8;
-                bf16x8 kb = *(const bf16x8*)&Klds[(cb * 16 + PI23(lr)) * SQ + d0];
-                sc = MFMA16(qfr[kc], kb, sc);
+                bf16x8 kb = *(const bf16x8*)&Klds[(cb * 16 + lr) * SQ + d0];
+                sc = MFMA16(kb, qfr[kc], sc);
                 bf16x8 vb = *(const bf16x8*)&Vlds[(cb * 16 + lr) * SQ + d0];
-                dp = MFMA16(dfr[kc], vb, dp);
+                dp = MFMA16(vb, dfr[kc], dp);
             }
-            uint32_t drop_cw = 0;
-            if constexpr (DROPOUT) drop_cw = drop_col_word(drop_hw, (uint32_t)(s0 + ks + cb * 16 + lr));
+            u32x4 cw = {};
+            if constexpr (DROPOUT) cw = *(const u32x4*)&Cw[cb * 16 + lg * 4];
             if (__builtin_amdgcn_readfirstlane(full_tile ? 1 : 0)) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pv = exp2f(sc[r] * (scale * DOL_LOG2E) - lsev[r]);
-                    float dpm = dp[r];
+                for (int x = 0; x < 4; ++x) {
+                    float pv = exp2f(fmaf(sc[x], scale2, -lsev));
+                    float dpm = dp[x];
                     if constexpr (DROPOUT)
-                        dpm = drop_keep_words(drop_rw[r], drop_cw, drop_thr) ? dp[r] * drop_rp : 0.f;
-                    dSw[(lg * 4 + r) * ST + cb * 16 + lr] = (__bf16)(pv * (dpm - delv[r]) * scale);
+                        dpm = drop_keep_words(drop_rw, cw[x], drop_thr) ? dp[x] * drop_rp : 0.f;
+                    dsf[cb >> 1][(cb & 1) * 4 + x] = (__bf16)(pv * (dpm - delv) * scale);
                 }
             } else {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int qpos = qs + wave * 16 + lg * 4 + r;
-                    const int kpos = ks + cb * 16 + lr;
-                    bool ok = qpos < L && kpos < kend_total && kpos <= qpos;
-                    float pv = ok ? exp2f(sc[r] * (scale * DOL_LOG2E) - lsev[r]) : 0.f;
-                    float dpm = dp[r];
+                for (int x = 0; x < 4; ++x) {
+                    const int kpos = ks + cb * 16 + lg * 4 + x;
+                    bool ok = qvalid && kpos < kend_total && kpos <= qrow;
+                    float pv = ok ? exp2f(fmaf(sc[x], scale2, -lsev)) : 0.f;
+                    float dpm = dp[x];
                     if constexpr (DROPOUT)
-                        dpm = drop_keep_words(drop_rw[r], drop_cw, drop_thr) ? dp[r] * drop_rp : 0.f;
-                    float ds = ok ? pv * (dpm - delv[r]) * scale : 0.f;
-                    dSw[(lg * 4 + r) * ST + cb * 16 + lr] = (__bf16)ds;
+                        dpm = drop_keep_words(drop_rw, cw[x], drop_thr) ? dp[x] * drop_rp : 0.f;
+                    float ds = ok ? pv * (dpm - delv) * scale : 0.f;
+                    dsf[cb >> 1][(cb & 1) * 4 + x] = (__bf16)ds;
                 }
             }
         }
 
-        // dQ += dS*K (contraction over this tile's keys) — pipelined tr16
-        // ladder over the PI23 K image
+        // dQ^T += K^T*dS^T (contraction over this tile's keys) — pipelined
+        // tr16 ladder over the K image; the image reads above were consumed
+        // by the score MFMAs, so no LDS op is outstanding when it opens
         {
-            bf16x8 dsf0 = *(const bf16x8*)&dSw[lr * ST + lg * 8];
-            bf16x8 dsf1 = *(const bf16x8*)&dSw[lr * ST + 32 + lg * 8];
-            lgkm_drain2x8(dsf0, dsf1);
             __builtin_amdgcn_sched_barrier(0);
             // depth-4 rotation: 3 fragments in flight per wait (the dq cap
             // has ~16 VGPR of headroom the dkv cap does not)
@@ -1384,7 +1352,7 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
         } else {                                                                                        \
             lgkm_wait2<0>(klo[(i) % 4], khi[(i) % 4]);                                                  \
         }                                                                                               \
-        dq[dc_] = MFMA16(kc2_ ? dsf1 : dsf0, tr16_join8(klo[(i) % 4], khi[(i) % 4]), dq[dc_]);          \
+        dq[dc_] = MFMA16(tr16_join8(klo[(i) % 4], khi[(i) % 4]), dsf[kc2_], dq[dc_]);                   \
     }
             DQ_STEP(0) DQ_STEP(1) DQ_STEP(2) DQ_STEP(3)
             DQ_STEP(4) DQ_STEP(5) DQ_STEP(6) DQ_STEP(7)
@@ -1395,17 +1363,18 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
         }
     }
 
-    // single bf16 store of the accumulated dQ straight into the packed dqkv
-    // (each (t, h, d) is owned by exactly one q-tile workgroup)
+    // single bf16 store of the accumulated dQ^T straight into the packed
+    // dqkv (each (t, h, d) is owned by exactly one q-tile workgroup): 4
+    // contiguous head-dim elements per lane and block (D % 8 == 0, so a
+    // group is all inside D or all pad)
+    __bf16* dqrow = dqkv_q + (int64_t)(s0 + (qvalid ? qrow : 0)) * q_ts + q_hoff;
 #pragma unroll
     for (int dc = 0; dc < DCH; ++dc) {
+        const int d0 = dc * 16 + lg * 4;
+        bf16x4 dv;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int qpos = qs + wave * 16 + lg * 4 + r;
-            const int d = dc * 16 + lr;
-            if (qpos < L && d < D)
-                dqkv_q[(int64_t)(s0 + qpos) * q_ts + q_hoff + d] = (__bf16)dq[dc][r];
-        }
+        for (int x = 0; x < 4; ++x) dv[x] = (__bf16)dq[dc][x];
+        if (qvalid && d0 < D) *(bf16x4*)&dqrow[d0] = dv;
     }
 }
 
@@ -1417,7 +1386,6 @@ static int launch_fa_bwd(hipStream_t stream, const __bf16* q, const __bf16* k, c
                          int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs,
                          int64_t v_ts, int64_t v_hs, int64_t do_ts, int max_tiles, float scale,
                          float p_drop, uint64_t seed) {
-    constexpr int ST = 64 + 8;
     dim3 block(512);
     dim3 grid(max_tiles, batch, H);
     constexpr int SQ = DPAD + 16;
@@ -1431,8 +1399,7 @@ static int launch_fa_bwd(hipStream_t stream, const __bf16* q, const __bf16* k, c
                        seed_lo, seed_hi, thr, rp);
     int err = dol_last_error();
     if (err) return err;
-    size_t shmem_dq = (size_t)(64 * SQ * 2 + 8 * 16 * ST) * sizeof(__bf16);
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD, DROPOUT>), grid, block, shmem_dq, stream,
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD, DROPOUT>), grid, block, FaKvLds<DPAD>::bytes(DROPOUT), stream,
                        q, k, v, dout, lse, delta, dqkv_q, cu, H, Hkv, D, G,
                        q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
                        seed_lo, seed_hi, thr, rp);

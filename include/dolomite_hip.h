@@ -133,7 +133,8 @@ int dolomite_rope_qkv(dolomite_stream_t stream,
  * (natural log, includes softmax scale), for backward.
  * cu_seqlens: (batch+1,) int32 device pointer; causal only. Attention
  * dropout: the *_dropout entry points below.
- * Error codes: 9010 dtype != bf16, 9011 D > 128.
+ * Error codes: 9010 dtype != bf16, 9011 D > 128, 9015 scale not > 0 (the
+ * forward takes each row's max on the unscaled scores).
  * ---------------------------------------------------------------------- */
 int dolomite_fa_varlen_fwd(dolomite_stream_t stream,
                            const void* q, const void* k, const void* v,

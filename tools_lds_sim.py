@@ -169,6 +169,61 @@ def main():
     # V^T reads: VSWZ8(dc*16+lr, kc2*32+lg*8) same as dOTl reads
     print("  (patterns identical to dkv rows, SV=SK strides)")
 
+    regfrag_images()
+
+
+def PI23(q):
+    return (q & ~12) | (((q >> 2) & 1) << 3) | (((q >> 3) & 1) << 2)
+
+
+def read_tr16(addrs):
+    """ds_read_b64_tr_b16 banks like ds_read_b64: 2 x 32 lanes, 2 dwords per
+    lane, bank = (a/4) % 64."""
+    return cycles(addrs, G32, 2, 64)
+
+
+def regfrag_images():
+    """The K/V images of fa_fwd / fa_bwd_dq with P / dS kept in registers
+    (S^T = K*Q^T): stride DPAD+16, three access patterns per image —
+    b128 staging writes, b128 row reads (score MFMAs) and the tr16 reads of
+    the second product in PERMUTED key order (read h of 32-key chunk c takes
+    row 32c + 16h + 4*(l>>4) + ((l>>2)&3), col d0 + 4*(l&3)). Natural row
+    order must be conflict-free for all three; PI23 placement, which the
+    8g+4h+jj order of the dkv ladders needs, is shown for contrast."""
+    print("== fa_fwd / fa_bwd_dq K,V images, register-resident P/dS ==")
+    for DPAD in (32, 64, 96, 128):
+        S = DPAD + 16
+        for place_name, place in (("natural", lambda r: r), ("PI23", PI23)):
+            wr = []
+            for base in range(0, 64 * DPAD // 8, 64):       # one wave-instruction per 64 pieces
+                addrs = {}
+                for l in range(64):
+                    pidx = base + l
+                    key, d0 = pidx // (DPAD // 8), (pidx % (DPAD // 8)) * 8
+                    addrs[l] = (place(key) * S + d0) * 2
+                wr.append(write128(addrs))
+            rd = []
+            for cb in range(4):
+                for kc in range(DPAD // 32):
+                    addrs = {}
+                    for l in range(64):
+                        lr, lg = lane_split(l)
+                        addrs[l] = (place(cb * 16 + lr) * S + kc * 32 + lg * 8) * 2
+                    rd.append(read128(addrs))
+            tr = []
+            for c in range(2):
+                for dc in range(DPAD // 16):
+                    for h in range(2):
+                        addrs = {}
+                        for l in range(64):
+                            row = 32 * c + 16 * h + 4 * (l >> 4) + ((l >> 2) & 3)
+                            addrs[l] = (place(row) * S + dc * 16 + 4 * (l & 3)) * 2
+                        tr.append(read_tr16(addrs))
+            print(f" DPAD={DPAD} stride={S} rows={place_name}")
+            report("staging b128 writes", wr)
+            report("b128 row reads (S^T / dP^T A-frags)", rd)
+            report("tr16 permuted-key reads (V^T / K^T A-frags)", tr)
+
 
 if __name__ == "__main__":
     main()
