@@ -5,6 +5,10 @@
 // over packed (total_q, heads, head_dim) with cu_seqlens, MHA/GQA/MQA head
 // layouts addressed in place on the fused c_attn projection output
 // (attention/base.py:72-81) via (t_stride, group_stride) addressing.
+// Sequences need not be back to back: the kernels take per-sequence row
+// spans [seq_begin[b], seq_end[b]) — (cu_seqlens, cu_seqlens + 1) for the
+// packed case, one span per row of a padded (B, S) batch for the dense
+// flash path of attention/flash.py ("Span entry points" below).
 //
 // Design (CDNA4-first):
 //   - MFMA v_mfma_f32_16x16x32_bf16 for both products; 64-wide waves.
@@ -329,7 +333,8 @@ template <int DPAD, bool DROPOUT>
 __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     __bf16* __restrict__ o, float* __restrict__ lse,
-    const int32_t* __restrict__ cu, int H, int Hkv, int D, int G,
+    const int32_t* __restrict__ seq_begin, const int32_t* __restrict__ seq_end,
+    int H, int Hkv, int D, int G,
     int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs, int64_t v_ts, int64_t v_hs,
     int64_t o_ts, int64_t T_total, float scale,
     uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
@@ -343,11 +348,11 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
 
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
-    // cu-derived values are wave-uniform: pin them to SGPRs so per-lane
+    // span-derived values are wave-uniform: pin them to SGPRs so per-lane
     // address arithmetic built on them does not hold VGPR pairs across the
     // main loop (measured: the compiler otherwise spills pointer pairs)
-    const int s0 = __builtin_amdgcn_readfirstlane(cu[b]);
-    const int L = __builtin_amdgcn_readfirstlane(cu[b + 1]) - s0;
+    const int s0 = __builtin_amdgcn_readfirstlane(seq_begin[b]);
+    const int L = __builtin_amdgcn_readfirstlane(seq_end[b]) - s0;
     // heaviest tiles (largest qs -> most k-tiles) dispatch FIRST: in-order
     // dispatch otherwise schedules the long-pole causal workgroups last
     // 8 waves x 16 rows = 128 q rows per workgroup: K/V staging and
@@ -619,26 +624,29 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
 
 template <int DPAD, bool DROPOUT>
 static int launch_fa_fwd(hipStream_t stream, const __bf16* q, const __bf16* k, const __bf16* v,
-                         __bf16* o, float* lse, const int32_t* cu, int batch, int64_t T,
-                         int H, int Hkv, int D, int G,
+                         __bf16* o, float* lse, const int32_t* seq_begin, const int32_t* seq_end,
+                         int batch, int64_t T, int H, int Hkv, int D, int G,
                          int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs,
                          int64_t v_ts, int64_t v_hs, int max_tiles, float scale,
                          float p_drop, uint64_t seed) {
     dim3 grid(max_tiles, batch, H), block(512);
     hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT>), grid, block, FaKvLds<DPAD>::bytes(DROPOUT), stream,
-                       q, k, v, o, lse, cu, H, Hkv, D, G,
+                       q, k, v, o, lse, seq_begin, seq_end, H, Hkv, D, G,
                        q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, (int64_t)H * D, T, scale,
                        (uint32_t)seed, (uint32_t)(seed >> 32), drop_threshold(p_drop),
                        1.f / (1.f - p_drop));
     return dol_last_error();
 }
 
-// shared by both forward entry points; p_drop == 0 runs the DROPOUT=false
-// instantiations (the dropout-free code)
+// shared by every forward entry point; p_drop == 0 runs the DROPOUT=false
+// instantiations (the dropout-free code). Sequence b is rows
+// [seq_begin[b], seq_end[b]); the varlen entry points pass
+// (cu_seqlens, cu_seqlens + 1).
 static int fa_varlen_fwd_dispatch(dolomite_stream_t stream,
                                   const void* q, const void* k, const void* v,
                                   void* o, float* lse,
-                                  const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                  const int32_t* seq_begin, const int32_t* seq_end,
+                                  int batch, int max_seqlen, int64_t T,
                                   int H, int Hkv, int D, int G,
                                   int64_t q_tstride, int64_t q_gstride,
                                   int64_t k_tstride, int64_t k_hstride,
@@ -648,12 +656,12 @@ static int fa_varlen_fwd_dispatch(dolomite_stream_t stream,
     if (D > 128) return 9011;
     if (!(scale > 0.f)) return 9015;  // the row max is taken before scaling
     // grid.x = tiles of the longest sequence; shorter sequences' surplus
-    // workgroups exit on the cu_seqlens check.
+    // workgroups exit on the span-length check.
     int max_tiles = (max_seqlen + 127) / 128;
     hipStream_t s = (hipStream_t)stream;
 #define CASE(DP, DROP)                                                                               \
     return launch_fa_fwd<DP, DROP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,          \
-                                   (__bf16*)o, lse, cu_seqlens, batch, T, H, Hkv, D, G, q_tstride,   \
+                                   (__bf16*)o, lse, seq_begin, seq_end, batch, T, H, Hkv, D, G, q_tstride, \
                                    q_gstride, k_tstride, k_hstride, v_tstride, v_hstride, max_tiles, \
                                    scale, p_drop, seed)
     if (p_drop > 0.f) {
@@ -678,7 +686,7 @@ extern "C" int dolomite_fa_varlen_fwd(dolomite_stream_t stream,
                                       int64_t k_tstride, int64_t k_hstride,
                                       int64_t v_tstride, int64_t v_hstride,
                                       float scale, int dtype) {
-    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, batch, max_seqlen, T,
+    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T,
                                   H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
                                   v_tstride, v_hstride, scale, dtype, 0.f, 0);
 }
@@ -693,7 +701,7 @@ extern "C" int dolomite_fa_varlen_fwd_dropout(dolomite_stream_t stream,
                                               int64_t v_tstride, int64_t v_hstride,
                                               float scale, int dtype, float p_drop, uint64_t seed) {
     if (!drop_p_valid(p_drop)) return 9013;  // p_drop outside [0, 1) (NaN included)
-    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, batch, max_seqlen, T,
+    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T,
                                   H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
                                   v_tstride, v_hstride, scale, dtype, p_drop, seed);
 }
@@ -834,7 +842,8 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     const __bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     float* __restrict__ dk_acc, float* __restrict__ dv_acc,
-    const int32_t* __restrict__ cu, int H, int Hkv, int D, int G,
+    const int32_t* __restrict__ seq_begin, const int32_t* __restrict__ seq_end,
+    int H, int Hkv, int D, int G,
     int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs, int64_t v_ts, int64_t v_hs,
     int64_t do_ts, int64_t T_total, float scale,
     uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
@@ -844,11 +853,11 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
     const int kvh = h / G;
-    // cu-derived values are wave-uniform: pin them to SGPRs so per-lane
+    // span-derived values are wave-uniform: pin them to SGPRs so per-lane
     // address arithmetic built on them does not hold VGPR pairs across the
     // main loop (measured: the compiler otherwise spills pointer pairs)
-    const int s0 = __builtin_amdgcn_readfirstlane(cu[b]);
-    const int L = __builtin_amdgcn_readfirstlane(cu[b + 1]) - s0;
+    const int s0 = __builtin_amdgcn_readfirstlane(seq_begin[b]);
+    const int L = __builtin_amdgcn_readfirstlane(seq_end[b]) - s0;
     // 8 waves x 16 keys = 128-key strip per workgroup
     const int ks = tile_id * 128;
     if (ks >= L) return;
@@ -1141,7 +1150,8 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     const __bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     __bf16* __restrict__ dqkv_q,
-    const int32_t* __restrict__ cu, int H, int Hkv, int D, int G,
+    const int32_t* __restrict__ seq_begin, const int32_t* __restrict__ seq_end,
+    int H, int Hkv, int D, int G,
     int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs, int64_t v_ts, int64_t v_hs,
     int64_t do_ts, int64_t T_total, float scale,
     uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
@@ -1151,11 +1161,11 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
     const int kvh = h / G;
-    // cu-derived values are wave-uniform: pin them to SGPRs so per-lane
+    // span-derived values are wave-uniform: pin them to SGPRs so per-lane
     // address arithmetic built on them does not hold VGPR pairs across the
     // main loop (measured: the compiler otherwise spills pointer pairs)
-    const int s0 = __builtin_amdgcn_readfirstlane(cu[b]);
-    const int L = __builtin_amdgcn_readfirstlane(cu[b + 1]) - s0;
+    const int s0 = __builtin_amdgcn_readfirstlane(seq_begin[b]);
+    const int L = __builtin_amdgcn_readfirstlane(seq_end[b]) - s0;
     // 8 waves x 16 rows = 128 q rows per workgroup; heaviest tiles first
     const int ntile_seq = (L + 127) / 128;
     if (tile_id >= ntile_seq) return;
@@ -1382,7 +1392,8 @@ template <int DPAD, bool DROPOUT>
 static int launch_fa_bwd(hipStream_t stream, const __bf16* q, const __bf16* k, const __bf16* v,
                          const __bf16* dout, const float* lse, const float* delta,
                          __bf16* dqkv_q, float* dk_acc, float* dv_acc,
-                         const int32_t* cu, int batch, int64_t T, int H, int Hkv, int D, int G,
+                         const int32_t* seq_begin, const int32_t* seq_end,
+                         int batch, int64_t T, int H, int Hkv, int D, int G,
                          int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs,
                          int64_t v_ts, int64_t v_hs, int64_t do_ts, int max_tiles, float scale,
                          float p_drop, uint64_t seed) {
@@ -1394,24 +1405,25 @@ static int launch_fa_bwd(hipStream_t stream, const __bf16* q, const __bf16* k, c
     const float rp = 1.f / (1.f - p_drop);
     size_t shmem_dkv = (size_t)(64 * (128 + 4) * 2 + 64 * SQ * 2) * sizeof(__bf16);
     hipLaunchKernelGGL((fa_bwd_dkv_kernel<DPAD, DROPOUT>), grid, block, shmem_dkv, stream,
-                       q, k, v, dout, lse, delta, dk_acc, dv_acc, cu, H, Hkv, D, G,
+                       q, k, v, dout, lse, delta, dk_acc, dv_acc, seq_begin, seq_end, H, Hkv, D, G,
                        q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
                        seed_lo, seed_hi, thr, rp);
     int err = dol_last_error();
     if (err) return err;
     hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD, DROPOUT>), grid, block, FaKvLds<DPAD>::bytes(DROPOUT), stream,
-                       q, k, v, dout, lse, delta, dqkv_q, cu, H, Hkv, D, G,
+                       q, k, v, dout, lse, delta, dqkv_q, seq_begin, seq_end, H, Hkv, D, G,
                        q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
                        seed_lo, seed_hi, thr, rp);
     return dol_last_error();
 }
 
-// shared by both backward entry points (see fa_varlen_fwd_dispatch)
+// shared by every backward entry point (see fa_varlen_fwd_dispatch)
 static int fa_varlen_bwd_dispatch(dolomite_stream_t stream,
                                   const void* q, const void* k, const void* v,
                                   const void* dout, const float* lse,
                                   const float* delta, void* dqkv_q, float* dk_acc, float* dv_acc,
-                                  const int32_t* cu_seqlens, int batch, int max_seqlen, int64_t T,
+                                  const int32_t* seq_begin, const int32_t* seq_end,
+                                  int batch, int max_seqlen, int64_t T,
                                   int H, int Hkv, int D, int G,
                                   int64_t q_tstride, int64_t q_gstride,
                                   int64_t k_tstride, int64_t k_hstride,
@@ -1425,7 +1437,7 @@ static int fa_varlen_bwd_dispatch(dolomite_stream_t stream,
 #define CASE(DP, DROP)                                                                                  \
     return launch_fa_bwd<DP, DROP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,             \
                                    (const __bf16*)dout, lse, delta, (__bf16*)dqkv_q, dk_acc, dv_acc,    \
-                                   cu_seqlens, batch, T, H, Hkv, D, G, q_tstride, q_gstride, k_tstride, \
+                                   seq_begin, seq_end, batch, T, H, Hkv, D, G, q_tstride, q_gstride, k_tstride, \
                                    k_hstride, v_tstride, v_hstride, do_tstride, max_tiles, scale,       \
                                    p_drop, seed)
     if (p_drop > 0.f) {
@@ -1453,7 +1465,7 @@ extern "C" int dolomite_fa_varlen_bwd(dolomite_stream_t stream,
                                       int64_t do_tstride,
                                       float scale, int dtype) {
     return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
-                                  cu_seqlens, batch, max_seqlen, T, H, Hkv, D, G,
+                                  cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T, H, Hkv, D, G,
                                   q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
                                   do_tstride, scale, dtype, 0.f, 0);
 }
@@ -1471,7 +1483,101 @@ extern "C" int dolomite_fa_varlen_bwd_dropout(dolomite_stream_t stream,
                                               float scale, int dtype, float p_drop, uint64_t seed) {
     if (!drop_p_valid(p_drop)) return 9013;
     return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
-                                  cu_seqlens, batch, max_seqlen, T, H, Hkv, D, G,
+                                  cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T, H, Hkv, D, G,
+                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
+                                  do_tstride, scale, dtype, p_drop, seed);
+}
+
+// ===========================================================================
+// Span entry points: sequences that are not back to back (a padded (B, S)
+// batch viewed as B*S rows). The attention kernels only ever touch rows
+// inside a span, so the rows between spans ("gap rows") are zeroed by a
+// kernel of their own — whole-buffer memsets would cost more than the
+// attention at the bench shape (1.3 GB of fp32 partials per launch).
+// ===========================================================================
+
+// Gap g of batch+1: rows [seq_end[g-1], seq_begin[g]) with seq_end[-1] = 0
+// and seq_begin[batch] = T. grid (chunks, batch+1); each gap is a contiguous
+// byte range (rows are contiguous), cleared with 16-byte stores in a
+// grid-stride loop. Both bounds are clamped into [0, T] and an inverted pair
+// is an empty range, so spans that break the precondition cannot push a
+// store outside the buffer.
+__global__ void __launch_bounds__(256) fa_zero_gap_rows_kernel(
+    uint4* __restrict__ buf, int64_t row_vec,
+    const int32_t* __restrict__ seq_begin, const int32_t* __restrict__ seq_end,
+    int batch, int64_t T) {
+    const int g = blockIdx.y;
+    int64_t lo = g == 0 ? 0 : (int64_t)seq_end[g - 1];
+    int64_t hi = g == batch ? T : (int64_t)seq_begin[g];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > T ? T : hi;
+    if (hi <= lo) return;
+    const int64_t first = lo * row_vec, last = hi * row_vec;   // 16-byte units
+    const uint4 z = {0u, 0u, 0u, 0u};
+    for (int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x; i < last;
+         i += (int64_t)gridDim.x * 256)
+        buf[i] = z;
+}
+
+extern "C" int dolomite_fa_zero_gap_rows(dolomite_stream_t stream, void* buf, int64_t row_bytes,
+                                         const int32_t* seq_begin, const int32_t* seq_end,
+                                         int batch, int64_t T) {
+    if (row_bytes <= 0 || row_bytes % 16 != 0) return 9016;
+    if (batch < 0 || T < 0 || batch >= 65535) return 9014;
+    if (T == 0) return 0;
+    // sized for the average gap if every row were a gap row (4 stores per
+    // thread); longer gaps take more trips of the grid-stride loop
+    const int64_t vec_per_gap = (T * (row_bytes / 16) + batch) / (batch + 1);
+    int64_t chunks = (vec_per_gap + 1023) / 1024;
+    chunks = chunks < 1 ? 1 : (chunks > 1024 ? 1024 : chunks);
+    hipLaunchKernelGGL(fa_zero_gap_rows_kernel, dim3((uint32_t)chunks, (uint32_t)(batch + 1)),
+                       dim3(256), 0, (hipStream_t)stream, (uint4*)buf, row_bytes / 16,
+                       seq_begin, seq_end, batch, T);
+    return dol_last_error();
+}
+
+extern "C" int dolomite_fa_spans_fwd(dolomite_stream_t stream,
+                                     const void* q, const void* k, const void* v,
+                                     void* o, float* lse,
+                                     const int32_t* seq_begin, const int32_t* seq_end,
+                                     int batch, int max_seqlen, int64_t T,
+                                     int H, int Hkv, int D, int G,
+                                     int64_t q_tstride, int64_t q_gstride,
+                                     int64_t k_tstride, int64_t k_hstride,
+                                     int64_t v_tstride, int64_t v_hstride,
+                                     float scale, int dtype, float p_drop, uint64_t seed) {
+    if (!drop_p_valid(p_drop)) return 9013;
+    if (dtype != DOLOMITE_BF16) return 9010;
+    if (D > 128) return 9011;
+    if (!(scale > 0.f)) return 9015;
+    // o's gap rows (disjoint from every row the attention kernel stores)
+    int err = dolomite_fa_zero_gap_rows(stream, o, (int64_t)H * D * (int64_t)sizeof(__bf16),
+                                        seq_begin, seq_end, batch, T);
+    if (err) return err;
+    if (batch == 0 || max_seqlen <= 0) return 0;  // every row is a gap row
+    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, seq_begin, seq_end, batch, max_seqlen, T,
+                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
+                                  v_tstride, v_hstride, scale, dtype, p_drop, seed);
+}
+
+extern "C" int dolomite_fa_spans_bwd(dolomite_stream_t stream,
+                                     const void* q, const void* k, const void* v,
+                                     const void* dout, const float* lse,
+                                     const float* delta, void* dqkv_q, float* dk_acc, float* dv_acc,
+                                     const int32_t* seq_begin, const int32_t* seq_end,
+                                     int batch, int max_seqlen, int64_t T,
+                                     int H, int Hkv, int D, int G,
+                                     int64_t q_tstride, int64_t q_gstride,
+                                     int64_t k_tstride, int64_t k_hstride,
+                                     int64_t v_tstride, int64_t v_hstride,
+                                     int64_t do_tstride,
+                                     float scale, int dtype, float p_drop, uint64_t seed) {
+    if (!drop_p_valid(p_drop)) return 9013;
+    if (dtype != DOLOMITE_BF16) return 9010;
+    if (D > 128) return 9011;
+    if (batch == 0 || max_seqlen <= 0) return 0;  // every row is a gap row
+    return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
+                                  seq_begin, seq_end, batch, max_seqlen, T, H, Hkv, D, G,
                                   q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
                                   do_tstride, scale, dtype, p_drop, seed);
 }

@@ -8,6 +8,9 @@ modeling_utils/attention/*). Three attention implementations:
     packed (T,) layout through the hand-written gfx950 kernels
     (fused RMSNorm+residual, packed-QKV RoPE, varlen flash attention,
     fused cross-entropy) behind the C-ABI in include/dolomite_hip.h.
+  - "flash_attention_2" on a dense (B, S) batch (attention/flash.py): the
+    same flash kernels in place on the padded buffer, one row span per
+    batch row — no (B, S, S) bias, no unpad / pad copies.
 
 Forward signature, list-input handling, loss semantics (boundary drops) and
 state-dict names match the reference exactly (drop-in boundary).
@@ -27,6 +30,7 @@ from ..ops import (
     fused_layernorm,
     fused_rmsnorm,
     rope_packed_qkv,
+    span_attention,
     varlen_attention,
 )
 from .config import GPTDolomiteConfig
@@ -314,7 +318,31 @@ class Attention(nn.Module):
             v = v.unsqueeze(1)
         return q, k, v
 
+    # ---- dense flash_attention_2: the padded batch on the flash kernels ----
+    def forward_dense_flash(self, hidden_states, spans, rope_cos_sin):
+        """The reference's dense flash path (attention/flash.py:95-135) without
+        its unpad / pad copies: the (B, S, row_len) c_attn output as
+        (B*S, row_len) IS the packed layout, with sequence b on the rows
+        spans = (seq_begin, seq_end, max_seqlen) name. Pad rows of the
+        attention output are zero (pad_input's semantics)."""
+        B, S, _ = hidden_states.shape
+        seq_begin, seq_end, max_seqlen = spans
+        qkv = self.c_attn(hidden_states.reshape(B * S, -1))  # (B*S, row_len)
+        if self.position_embedding_type == "rope":
+            cos, sin = rope_cos_sin  # (B*S, D) fp32
+            qkv = rope_packed_qkv(qkv, cos, sin, self.layout)
+        attn_output = span_attention(
+            qkv, seq_begin, seq_end, max_seqlen, self.layout, self.softmax_scale,
+            dropout_p=self.attn_pdrop if self.training else 0.0,
+        )
+        attn_output = self.c_proj(attn_output.view(B, S, -1))
+        return self.resid_dropout(attn_output)
+
     def forward_dense(self, hidden_states, attention_bias, rope_cos_sin, implementation):
+        if implementation == "flash_attention_2":
+            # attention_bias carries the row spans here, rope_cos_sin the
+            # (B*S, D) fp32 tables (GPTDolomiteModel.dense_flash_inputs)
+            return self.forward_dense_flash(hidden_states, attention_bias, rope_cos_sin)
         B, S, _ = hidden_states.shape
         H, Hkv, D = self.num_heads, self.num_key_value_heads, self.head_dim
         q, k, v = self._split_dense(self.c_attn(hidden_states))
@@ -564,7 +592,7 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
         elif self.position_embedding_type == "alibi":
             # reference base.py:261-287 + alibi.py; supported on the dense
             # eager/sdpa paths (the reference's flash path drops it too)
-            assert not self._use_padding_free_transformer, (
+            assert self.attention_implementation != "flash_attention_2", (
                 "alibi is not supported on the padding-free/flash path (matches the reference)"
             )
             self.alibi = Alibi(config.n_head)
@@ -636,6 +664,48 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
         hidden_states, _ = self.ln_f(delta, residual)
         return hidden_states
 
+    # ---- dense flash_attention_2: spans and rope tables, once per forward ----
+    def dense_flash_inputs(self, attention_mask, position_ids, B: int, S: int, device, dtype):
+        """What Attention.forward_dense_flash needs for a padded (B, S) batch
+        viewed as B*S rows: ((seq_begin, seq_end, max_seqlen), rope_cos_sin).
+        Row b's sequence is its run of set mask positions, rows
+        [b*S + first_b, b*S + first_b + count_b): right or left padding alike,
+        an all-zero row is an empty span. No mask: every row is full and
+        nothing is read back. With a mask ONE host readback gives max_seqlen
+        and the contiguity check (the reference's get_unpad_data also takes
+        one .item()); a row with a hole raises — the flash kernels are causal
+        over one contiguous run and there is no silent fallback."""
+        assert B * S < 2**31, "row indices are int32"
+        row0 = torch.arange(B, dtype=torch.int64, device=device) * S
+        if attention_mask is None:
+            seq_begin, seq_end, max_seqlen = row0, row0 + S, S
+        else:
+            if attention_mask.shape != (B, S):
+                raise ValueError(f"attention_mask must be (B, S) = {(B, S)}, got {tuple(attention_mask.shape)}")
+            m = attention_mask.to(device) != 0
+            m8 = m.to(torch.int8)
+            count = m.sum(-1)
+            first = m8.argmax(-1)                    # 0 for an all-zero row
+            last = S - 1 - m8.flip(-1).argmax(-1)
+            contiguous = ((last - first + 1 == count) | (count == 0)).all()
+            max_seqlen, ok = torch.stack([count.max(), contiguous.to(count.dtype)]).tolist()
+            if not ok:
+                raise ValueError(
+                    "flash_attention_2 needs every attention_mask row to be one contiguous run of "
+                    "set positions (right or left padding); a mask with holes needs sdpa or eager"
+                )
+            seq_begin = row0 + first
+            seq_end = seq_begin + count
+        spans = (seq_begin.to(torch.int32), seq_end.to(torch.int32), int(max_seqlen))
+
+        rope_cos_sin = None
+        if self.position_embedding_type == "rope":
+            cos, sin = self.rope(S, device)  # (S, D) fp32
+            # same table rounding as the padding-free path
+            pos = position_ids.reshape(-1)
+            rope_cos_sin = (cos.to(dtype).float()[pos].contiguous(), sin.to(dtype).float()[pos].contiguous())
+        return spans, rope_cos_sin
+
     # ---- dense eager/sdpa path ----
     def _forward_dense(self, input_ids, attention_mask, position_ids, token_type_ids):
         B, S = input_ids.shape
@@ -652,15 +722,21 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
         if self.m_emb is not None:
             hs = hs * self.m_emb
 
+        flash = self.attention_implementation == "flash_attention_2"
         rope_cos_sin = None
-        if self.position_embedding_type == "rope":
+        if self.position_embedding_type == "rope" and not flash:
             cos, sin = self.rope(S, device)
             cos = cos.to(hs.dtype)[position_ids].unsqueeze(1)  # (B, 1, S, D)
             sin = sin.to(hs.dtype)[position_ids].unsqueeze(1)
             rope_cos_sin = (cos, sin)
 
         attention_bias = None
-        if attention_mask is not None:
+        if flash:
+            # no (B, S, S) bias: the blocks get the row spans in its place
+            attention_bias, rope_cos_sin = self.dense_flash_inputs(
+                attention_mask, position_ids, B, S, device, hs.dtype
+            )
+        elif attention_mask is not None:
             # (B, S) padding mask & causal -> additive float bias
             # (reference base.py:299-350, 553-580)
             causal = torch.ones(S, S, dtype=torch.bool, device=device).tril().unsqueeze(0)

@@ -250,15 +250,21 @@ class MoEDolomiteModel(GPTDolomiteModel):
             hs = self.drop(hs)
             if self.m_emb is not None:
                 hs = hs * self.m_emb
+            flash = self.attention_implementation == "flash_attention_2"
             rope_cos_sin = None
-            if self.position_embedding_type == "rope":
+            if self.position_embedding_type == "rope" and not flash:
                 cos, sin = self.rope(S, device)
                 rope_cos_sin = (
                     cos.to(hs.dtype)[position_ids].unsqueeze(1),
                     sin.to(hs.dtype)[position_ids].unsqueeze(1),
                 )
             attention_bias = None
-            if attention_mask is not None:
+            if flash:
+                # row spans in the bias slot (GPTDolomiteModel.dense_flash_inputs)
+                attention_bias, rope_cos_sin = self.dense_flash_inputs(
+                    attention_mask, position_ids, B, S, device, hs.dtype
+                )
+            elif attention_mask is not None:
                 causal = torch.ones(S, S, dtype=torch.bool, device=device).tril().unsqueeze(0)
                 allowed = causal & attention_mask.unsqueeze(1).to(torch.bool)
                 bias = torch.zeros(B, S, S, dtype=hs.dtype, device=device)

@@ -10,6 +10,7 @@ from .functional import (
     fused_rmsnorm,
     grouped_expert_gemm,
     rope_packed_qkv,
+    span_attention,
     varlen_attention,
 )
 from .hip import is_available as hip_extension_available

@@ -436,15 +436,21 @@ def _drop_scale(p: float) -> float:
     return float(one / (one - torch.tensor(float(p), dtype=torch.float32)))
 
 
-def _attn_fwd_cpu(qkv, cu, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
-    """fp32-softmax varlen attention + lse, CPU restatement of the kernel."""
+def _cu_spans(cu):
+    """cu_seqlens -> the (begins, ends) lists of back-to-back sequences."""
+    cul = cu.tolist()
+    return cul[:-1], cul[1:]
+
+
+def _attn_fwd_cpu(qkv, begins, ends, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
+    """fp32-softmax causal attention + lse over the row spans
+    [begins[i], ends[i]) of the packed qkv, CPU restatement of the kernel.
+    Rows outside every span: o is zero, lse is zero (unspecified on GPU)."""
     q, k, v = lo.unpack_cpu(qkv)
     T = q.shape[0]
-    o = torch.empty(T, lo.H * lo.D, dtype=qkv.dtype)
-    lse = torch.empty(lo.H, T, dtype=torch.float32)
-    cul = cu.tolist()
-    for i in range(len(cul) - 1):
-        s, e = cul[i], cul[i + 1]
+    o = torch.zeros(T, lo.H * lo.D, dtype=qkv.dtype)
+    lse = torch.zeros(lo.H, T, dtype=torch.float32)
+    for s, e in zip(begins, ends):
         if e == s:
             continue
         qi = q[s:e].float()
@@ -503,7 +509,7 @@ class VarlenAttention(torch.autograd.Function):
                 else:
                     hip.check(hip.lib().dolomite_fa_varlen_fwd(*args), "fa_varlen_fwd")
         else:
-            o, lse = _attn_fwd_cpu(qkv, cu_seqlens, scale, lo, dropout_p, seed)
+            o, lse = _attn_fwd_cpu(qkv, *_cu_spans(cu_seqlens), scale, lo, dropout_p, seed)
         ctx.save_for_backward(qkv, o, lse, cu_seqlens)
         ctx.layout = lo
         ctx.scale = scale
@@ -560,21 +566,24 @@ class VarlenAttention(torch.autograd.Function):
         # CPU: differentiate the CPU restatement with torch autograd
         qkv_l = qkv.detach().requires_grad_(True)
         with torch.enable_grad():
-            o2, _ = _attn_fwd_cpu_autograd(qkv_l, cu, ctx.scale, lo, ctx.dropout_p, ctx.seed)
+            o2, _ = _attn_fwd_cpu_autograd(qkv_l, *_cu_spans(cu), ctx.scale, lo, ctx.dropout_p, ctx.seed)
             (dqkv,) = torch.autograd.grad(o2, qkv_l, dout)
         return dqkv, None, None, None, None, None, None
 
 
-def _attn_fwd_cpu_autograd(qkv, cu, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
+def _attn_fwd_cpu_autograd(qkv, begins, ends, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
+    """Differentiable twin of _attn_fwd_cpu (spans ascending and disjoint):
+    gap rows are constant zeros, so no gradient reaches their qkv rows."""
     q, k, v = lo.unpack_cpu(qkv)
     T = q.shape[0]
-    outs = []
-    cul = cu.tolist()
     pieces = []
-    for i in range(len(cul) - 1):
-        s, e = cul[i], cul[i + 1]
+    row = 0  # rows emitted so far
+    for s, e in zip(begins, ends):
         if e == s:
             continue
+        if s > row:
+            pieces.append(qkv.new_zeros(s - row, lo.H * lo.D))
+        row = e
         qi = q[s:e].float()
         ki = k[s:e].float()
         vi = v[s:e].float()
@@ -594,7 +603,9 @@ def _attn_fwd_cpu_autograd(qkv, cu, scale, lo: QKVLayout, dropout_p: float = 0.0
                 p = p * keep[h] * rp
             hs.append(p @ vi[:, j])
         pieces.append(torch.cat(hs, dim=-1).to(qkv.dtype))
-    o = torch.cat(pieces, dim=0)
+    if T > row:
+        pieces.append(qkv.new_zeros(T - row, lo.H * lo.D))
+    o = torch.cat(pieces, dim=0) if pieces else qkv.new_zeros(0, lo.H * lo.D)
     return o, None
 
 
@@ -612,6 +623,134 @@ def varlen_attention(qkv, cu_seqlens, max_seqlen, layout: QKVLayout, scale: floa
     if seed is None:
         seed = draw_attention_dropout_seed()
     return VarlenAttention.apply(qkv, cu_seqlens, int(max_seqlen), layout, scale, dropout_p, int(seed))
+
+
+class SpanAttention(torch.autograd.Function):
+    """Causal attention over sequences that are NOT back to back: sequence b
+    is rows [seq_begin[b], seq_end[b]) of the packed qkv (T, row_len) — a
+    padded (B, S) batch viewed as B*S rows, run in place. The dense
+    flash_attention_2 replacement (attention/flash.py:95-135) without its
+    unpad / pad copies. Rows outside every span: o and dqkv are exactly zero
+    (pad_input's semantics). Same kernels as VarlenAttention."""
+
+    @staticmethod
+    def forward(ctx, qkv, seq_begin, seq_end, max_seqlen: int, layout: QKVLayout, scale: float,
+                dropout_p: float = 0.0, seed: int = 0):
+        lo = layout
+        T = qkv.shape[0]
+        batch = seq_begin.shape[0]
+        dropout_p = float(dropout_p)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if qkv.is_cuda:
+            qkv = qkv.contiguous()
+            o = torch.empty(T, lo.H * lo.D, dtype=qkv.dtype, device=qkv.device)
+            lse = torch.empty(lo.H, T, dtype=torch.float32, device=qkv.device)
+            with hip.prof("fa_spans_fwd"):
+                hip.check(
+                    hip.lib().dolomite_fa_spans_fwd(
+                        hip.stream(),
+                        hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
+                        hip.ptr(o), hip.ptr(lse), hip.ptr(seq_begin), hip.ptr(seq_end),
+                        batch, int(max_seqlen), T, lo.H, lo.Hkv, lo.D, lo.G,
+                        lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
+                        lo.row_len, lo.kv_hstride, float(scale), hip.dt(qkv), dropout_p, seed,
+                    ),
+                    "fa_spans_fwd",
+                )
+        else:
+            o, lse = _attn_fwd_cpu(qkv, seq_begin.tolist(), seq_end.tolist(), scale, lo, dropout_p, seed)
+        ctx.save_for_backward(qkv, o, lse, seq_begin, seq_end)
+        ctx.layout = lo
+        ctx.scale = scale
+        ctx.max_seqlen = int(max_seqlen)
+        ctx.dropout_p = dropout_p
+        ctx.seed = seed
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, o, lse, seq_begin, seq_end = ctx.saved_tensors
+        lo: QKVLayout = ctx.layout
+        T = qkv.shape[0]
+        batch = seq_begin.shape[0]
+        if qkv.is_cuda:
+            dout = dout.contiguous()
+            delta = torch.empty(lo.H, T, dtype=torch.float32, device=qkv.device)
+            hip.check(
+                hip.lib().dolomite_fa_bwd_preprocess(
+                    hip.stream(), hip.ptr(o), hip.ptr(dout), hip.ptr(delta),
+                    T, lo.H, lo.D, lo.H * lo.D, lo.H * lo.D, hip.dt(qkv),
+                ),
+                "fa_bwd_preprocess",
+            )
+            # span rows of the partials and of dqkv are stored exclusively by
+            # the kernels; gap rows are left as allocated, reduced as they are
+            # by the finalize, and zeroed in dqkv afterwards (no whole-buffer
+            # memset: the partials are the largest buffers of the step)
+            dk_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
+            dv_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
+            dqkv = torch.empty_like(qkv)
+            with hip.prof("fa_spans_bwd"):
+                hip.check(
+                    hip.lib().dolomite_fa_spans_bwd(
+                        hip.stream(),
+                        hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
+                        hip.ptr(dout), hip.ptr(lse), hip.ptr(delta), hip.ptr(dqkv),
+                        hip.ptr(dk_acc), hip.ptr(dv_acc),
+                        hip.ptr(seq_begin), hip.ptr(seq_end), batch, ctx.max_seqlen, T,
+                        lo.H, lo.Hkv, lo.D, lo.G,
+                        lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
+                        lo.row_len, lo.kv_hstride, lo.H * lo.D, float(ctx.scale), hip.dt(qkv),
+                        ctx.dropout_p, ctx.seed,
+                    ),
+                    "fa_spans_bwd",
+                )
+            hip.check(
+                hip.lib().dolomite_fa_grad_finalize(
+                    hip.stream(), hip.ptr(dk_acc), hip.ptr(dv_acc), hip.ptr(dqkv),
+                    T, lo.Hkv, lo.D, lo.G, lo.row_len,
+                    lo.k_off, lo.kv_hstride, lo.v_off, hip.dt(qkv),
+                ),
+                "fa_grad_finalize",
+            )
+            with hip.prof("fa_zero_gap_rows"):
+                hip.check(
+                    hip.lib().dolomite_fa_zero_gap_rows(
+                        hip.stream(), hip.ptr(dqkv), lo.row_len * dqkv.element_size(),
+                        hip.ptr(seq_begin), hip.ptr(seq_end), batch, T,
+                    ),
+                    "fa_zero_gap_rows",
+                )
+            return dqkv, None, None, None, None, None, None, None
+        # CPU: differentiate the CPU restatement with torch autograd
+        qkv_l = qkv.detach().requires_grad_(True)
+        with torch.enable_grad():
+            o2, _ = _attn_fwd_cpu_autograd(qkv_l, seq_begin.tolist(), seq_end.tolist(), ctx.scale, lo,
+                                           ctx.dropout_p, ctx.seed)
+            (dqkv,) = torch.autograd.grad(o2, qkv_l, dout)
+        return dqkv, None, None, None, None, None, None, None
+
+
+def span_attention(qkv, seq_begin, seq_end, max_seqlen, layout: QKVLayout, scale: float,
+                   dropout_p: float = 0.0, seed: int | None = None):
+    """Causal attention over the row spans [seq_begin[b], seq_end[b]) of the
+    packed qkv (T, row_len); int32 (batch,) tensors on qkv's device with
+    0 <= begin <= end <= T, ascending and disjoint, empty spans allowed.
+    max_seqlen is the longest span. Output (T, H*D) with zeros on the rows
+    outside every span. Dropout as in varlen_attention: the keep mask is a
+    function of the global row indices of the buffer."""
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
+    if seq_begin.shape != seq_end.shape or seq_begin.dim() != 1:
+        raise ValueError("seq_begin and seq_end must be 1-D tensors of one length")
+    if seq_begin.dtype != torch.int32 or seq_end.dtype != torch.int32:
+        raise TypeError("seq_begin and seq_end must be int32")
+    if dropout_p == 0.0:  # no draw: the RNG stream of p = 0 runs is untouched
+        return SpanAttention.apply(qkv, seq_begin, seq_end, int(max_seqlen), layout, scale, 0.0, 0)
+    if seed is None:
+        seed = draw_attention_dropout_seed()
+    return SpanAttention.apply(qkv, seq_begin, seq_end, int(max_seqlen), layout, scale, dropout_p, int(seed))
 
 
 # ---------------------------------------------------------------------------

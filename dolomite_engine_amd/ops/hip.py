@@ -58,6 +58,18 @@ _SIGNATURES = {
          _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
         _i32,
     ),
+    # the *_dropout pair with (seq_begin, seq_end) in place of cu_seqlens
+    "dolomite_fa_spans_fwd": (
+        [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
+        _i32,
+    ),
+    "dolomite_fa_spans_bwd": (
+        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
+        _i32,
+    ),
+    "dolomite_fa_zero_gap_rows": ([_p, _p, _i64, _p, _p, _i32, _i64], _i32),
     "dolomite_fa_dropout_mask_probe": ([_p, _p, _u64, _f32, _i32, _i64, _i32, _i64, _i32], _i32),
     "dolomite_fa_grad_finalize": ([_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32], _i32),
     "dolomite_ce_fwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),

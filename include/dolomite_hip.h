@@ -232,6 +232,62 @@ int dolomite_fa_varlen_bwd_dropout(dolomite_stream_t stream,
                                    int64_t do_tstride,
                                    float scale, int dtype, float p_drop, uint64_t seed);
 
+/* ------------------------------------------------------------------------
+ * Span attention: the same kernels over sequences that are NOT back to back.
+ * Replaces the reference's dense flash path (attention/flash.py: unpad by the
+ * mask, flash_attn_varlen_func, pad_input) without the unpad / pad copies: a
+ * padded (B, S, row_len) batch viewed as (B*S, row_len) is the packed layout
+ * with sequence b on rows [seq_begin[b], seq_end[b]).
+ *
+ * seq_begin, seq_end: (batch,) int32 device pointers. Precondition:
+ *   0 <= seq_begin[b] <= seq_end[b] <= T, spans ascending and disjoint
+ *   (seq_end[b] <= seq_begin[b+1]); empty spans are allowed.
+ * max_seqlen: the longest span. (cu_seqlens, cu_seqlens + 1) is the
+ * back-to-back special case the varlen entry points pass.
+ * Rows outside every span ("gap rows": [seq_end[b-1], seq_begin[b]) with
+ * seq_end[-1] = 0 and seq_begin[batch] = T):
+ *   - dolomite_fa_spans_fwd leaves o exactly zero there (pad_input's
+ *     semantics); lse is unspecified there.
+ *   - dolomite_fa_spans_bwd writes nothing there (dqkv_q, dk_acc, dv_acc);
+ *     dolomite_fa_grad_finalize then reduces whatever the partials hold on
+ *     those rows, so the host runs dolomite_fa_zero_gap_rows on dqkv AFTER
+ *     the finalize: q, k and v slots of every gap row end exactly zero.
+ *   - delta from dolomite_fa_bwd_preprocess is unspecified there and never
+ *     read.
+ * Dropout: t_q / t_k of the keep-mask stay the GLOBAL row indices of the
+ * buffer (b*S + position for a padded batch). p_drop == 0 runs the
+ * dropout-free kernels. The other arguments and the error codes are those of
+ * dolomite_fa_varlen_fwd_dropout / _bwd_dropout.
+ * ---------------------------------------------------------------------- */
+int dolomite_fa_spans_fwd(dolomite_stream_t stream,
+                          const void* q, const void* k, const void* v,
+                          void* o, float* lse,
+                          const int32_t* seq_begin, const int32_t* seq_end,
+                          int batch, int max_seqlen, int64_t T,
+                          int H, int Hkv, int D, int G,
+                          int64_t q_tstride, int64_t q_gstride,
+                          int64_t k_tstride, int64_t k_hstride,
+                          int64_t v_tstride, int64_t v_hstride,
+                          float scale, int dtype, float p_drop, uint64_t seed);
+int dolomite_fa_spans_bwd(dolomite_stream_t stream,
+                          const void* q, const void* k, const void* v,
+                          const void* dout, const float* lse,
+                          const float* delta, void* dqkv_q, float* dk_acc, float* dv_acc,
+                          const int32_t* seq_begin, const int32_t* seq_end,
+                          int batch, int max_seqlen, int64_t T,
+                          int H, int Hkv, int D, int G,
+                          int64_t q_tstride, int64_t q_gstride,
+                          int64_t k_tstride, int64_t k_hstride,
+                          int64_t v_tstride, int64_t v_hstride,
+                          int64_t do_tstride,
+                          float scale, int dtype, float p_drop, uint64_t seed);
+/* Zero the gap rows of a (T, row_bytes) row-major buffer, touching no span
+ * row. buf must be 16-byte aligned; error 9016 if row_bytes is not a
+ * positive multiple of 16, 9014 for batch < 0 or T < 0. */
+int dolomite_fa_zero_gap_rows(dolomite_stream_t stream, void* buf, int64_t row_bytes,
+                              const int32_t* seq_begin, const int32_t* seq_end,
+                              int batch, int64_t T);
+
 /* Keep-mask probe: out[(h*nq + i)*nk + j] = keep(seed, h, tq0+i, tk0+j, p_drop)
  * as 0/1 bytes for h in [0, H), through the device function the attention
  * kernels use. out: (H, nq, nk) uint8 device pointer. Errors: 9013 as above,
