@@ -35,7 +35,9 @@
 //     deterministic gradients; dq uses the forward's orientation (S^T and
 //     dP^T with the q row on the lane, dS packed in registers into
 //     dQ^T = K^T*dS^T) and stores bf16 straight into the packed dqkv. dkv
-//     contracts over q and still routes P^T / dS^T through LDS strips.
+//     contracts over q with the KEY on the lane (S = Q*K^T, dP = dO*V^T),
+//     so its P / dS also pack in registers, into dV^T = dO^T*P and
+//     dK^T = Q^T*dS — no kernel routes P or dS through LDS.
 //   - attention dropout (flash_attn_varlen_func's dropout_p) is fused: the
 //     keep-mask is a pure counter-based hash of (seed, q-head, global q
 //     token, global k token) — see "Attention dropout keep-mask" below and
@@ -78,11 +80,12 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // Conflicts (tools_lds_sim.py, validated against SQ_LDS_BANK_CONFLICT):
 // with S=112 the natural row order 2-way conflicts for THIS row pattern
 // (rows 0 and 8 alias); storing image rows with bits 2 and 3 SWAPPED makes
-// both the tr reads and the b128 row-major B-frag reads conflict-free. The
-// dkv images, read in this order, use PI23 row placement (writers and
-// readers alike). The fwd / dq ladders read in the permuted key order of
-// "Swapped-operand score tiles" (8 consecutive rows per 32-lane pass), which
-// is conflict-free in natural order and 2-way conflicted under PI23.
+// both the tr reads and the b128 row-major B-frag reads conflict-free
+// (lds_tr16_bfrag / dolomite_tr16_bfrag_probe keep that reader). The fwd /
+// dq / dkv ladders read in the permuted order of "Swapped-operand score
+// tiles" (8 consecutive rows per 32-lane pass), which is conflict-free in
+// natural row order and 2-way conflicted under PI23: all three use natural
+// rows.
 // ---------------------------------------------------------------------------
 #define PI23(q) (((q) & ~12) | ((((q) >> 2) & 1) << 3) | ((((q) >> 3) & 1) << 2))
 
@@ -128,15 +131,15 @@ __device__ __forceinline__ bf16x8 lds_tr16_bfrag(const __bf16* img, int rowbase,
 // counter never drains to 0 inside the loop.
 //
 // Count discipline: the ladder's waits are exact only if no OTHER lgkm op
-// is outstanding, so each region (a) opens with nothing in flight — dkv
-// drains its strip writes; in fwd / dq every earlier LDS read has already
-// been consumed by a score MFMA — and (b) is fenced with sched_barrier(0)
+// is outstanding, so each region (a) opens with nothing in flight — every
+// earlier LDS read has already been consumed by a score MFMA or the
+// softmax — and (b) is fenced with sched_barrier(0)
 // so the compiler cannot move its own ds/smem ops inside.
 // ---------------------------------------------------------------------------
 
 // Issue one B-fragment's two transpose reads (no wait): OFF = byte offset of
-// the (rowbase, d0) chunk inside the image, a0/a1 = the lane's two PI23 row
-// base addresses (computed once per kernel).
+// the (rowbase, d0) chunk inside the image, a0/a1 = the lane's two row base
+// addresses (computed once per kernel).
 template <int OFF>
 __device__ __forceinline__ void tr16_issue(unsigned a0, unsigned a1, bf16x4& lo, bf16x4& hi) {
     asm volatile(
@@ -819,24 +822,57 @@ extern "C" int dolomite_fa_bwd_preprocess(dolomite_stream_t stream,
 //     once. Row-major K and V images, staged per kv tile; dS stays in
 //     registers (see "Swapped-operand score tiles").
 
-// dkv round-2 structure: NO transposed LDS images. The Q/dO images are
-// stored row-major with PI23 row placement only, read two ways:
-//   - S^T/dP^T B-fragments: b128 row reads (row cb*16+PI23(lr), conflict-free
-//     at stride DPAD+16 per tools_lds_sim.py);
-//   - dK/dV B-fragments: ds_read_b64_tr_b16 ladder (same PI23 image).
-// This removes 2*DPAD*96 elements of LDS (102 KB -> 64 KB at DPAD=96) and
-// the 16 scalar b16 scatter-writes per staged piece. Together with the
-// __launch_bounds__(512, 4) register cap (<=128 VGPR) the kernel reaches
-// 2 workgroups/CU: while one workgroup stages Q/dO from HBM the co-resident
-// one runs its MFMA segments — the cross-workgroup latency hiding the
-// round-1 single-occupancy version lacked.
-// Occupancy bound: <=96 head-dim fits the 128-VGPR / 64-KB-LDS budget for
-// 2 workgroups/CU (measured: 128 VGPR, 3 prologue spills); the 128 variant
-// does not (43 spills into the hot loop at the cap) and keeps 1 WG/CU.
-// Dropout (DROPOUT=true): the P^T strip feeding dV holds M ? P : 0 and dV is
+// dkv structure: the key on the lane, P and dS in registers. A wave owns 16
+// keys of the workgroup's 128-key strip and holds their K / V rows as
+// register fragments for the whole kernel; the Q / dO tile (64 queries) is
+// staged as two row-major LDS images in natural row order (stride DPAD+16,
+// the fwd / dq geometry), read two ways:
+//   - S = Q*K^T and dP = dO*V^T: the image row is the A operand (b128 row
+//     reads), the K / V register fragment the B operand (the A and B lane
+//     maps are symmetric), so C block cb holds, on lane l reg x,
+//       key  l & 15            query  16*cb + 4*(l>>4) + x;
+//   - the 8 values of query blocks (2c, 2c+1) pack, with no lane movement
+//     and no LDS, into the B operand of dV^T += dO^T*P and dK^T += Q^T*dS
+//     over a 32-query chunk. Element e on lane group g is query
+//     32c + 16*(e>>2) + 4g + (e&3); the A operands are tr16 reads of the
+//     same images in that order (fa_tr16_perm_bases, as the fwd / dq
+//     ladders do for keys). One chunk at a time: 4 + 4 packed registers
+//     of P / dS are live, then that chunk's 2*DCH ladder MFMAs.
+// The per-query lse and delta (and, with dropout, the row words of the keep
+// mask) are staged once per tile into 64-entry LDS arrays by one wave each:
+// a lane needs 4 consecutive query rows per block and the packed row offset
+// s0 is arbitrary, so the global rows are only 4-byte aligned, while the LDS
+// arrays are tile-relative and read as one b128 (broadcast over the 16 lanes
+// of a group). Rows >= L are staged as 0 and masked. -delta is the INITIAL
+// accumulator of the dP chain (no dropout), and the softmax scale of dS is
+// applied once to dK at the store.
+// Outputs come out transposed (head-dim 16*dc + 4g + x on the registers, key
+// on l & 15): one 16-byte non-temporal store per lane, block and buffer.
+// __launch_bounds__(512, 4) (<= 128 VGPR) gives 2 workgroups/CU at
+// DPAD <= 96: while one workgroup stages Q/dO from HBM the co-resident one
+// runs its MFMA segments. DPAD = 128 keeps the looser bound of its parent.
+// Dropout (DROPOUT=true): the P fragment feeding dV holds M ? P : 0 and dV is
 // scaled by rp = 1/(1-p) once at the store; dS uses the UNDROPPED P with the
 // masked, scaled dP: dS = P * ((M ? dP*rp : 0) - delta) * scale (delta =
-// rowsum(dO*O) already equals sum_j P_ij * dP_ij under dropout).
+// rowsum(dO*O) already equals sum_j P_ij * dP_ij under dropout). The lane's
+// key is fixed -> one hoisted column word; 4 row words per block from LDS.
+
+// P = 2^(s*scale*log2e - lse*log2e) as ONE v_exp_f32: exp2f() wraps the
+// instruction in a 5-instruction rescale so that results below 2^-126 come
+// out as denormals; such a probability is 0 in every product it enters here,
+// and the bare instruction returns exactly that. The issue-bound softmax
+// body drops from ~10 to ~5 VALU instructions per score.
+__device__ __forceinline__ float dkv_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+template <int DPAD>
+struct FaDkvLds {
+    static constexpr int S = DPAD + 16;
+    static constexpr size_t image_bytes = (size_t)2 * 64 * S * sizeof(__bf16);  // multiple of 256
+    static constexpr size_t bytes(bool dropout) {
+        return image_bytes + 2 * 64 * sizeof(float) + (dropout ? 64 * sizeof(uint32_t) : 0);
+    }
+};
+
 template <int DPAD, bool DROPOUT>
 __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
@@ -867,26 +903,17 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     const int lr = lane & 15;
     const int lg = lane >> 4;
 
-    constexpr int SQ = DPAD + 16;              // PI23-rowed image stride
-    // Transposed [q][key] strips: each lane's 4 C-rows (keys) are contiguous
-    // along the key axis, so the softmax emits ONE ds_write_b64 per strip
-    // per q-block instead of 4 scalar b16 stores (32 -> 8 write
-    // instructions per wave per tile; the LDS store path was a measured
-    // co-bottleneck). Read back as MFMA A-fragments via the tr16 ladder.
-    // Stride 132: rows stay 8-byte aligned (ds_write_b64 / tr16 reads need
-    // natural alignment — stride*2 must be a multiple of 8; the odd
-    // half-stride that would fully de-conflict the write groups is
-    // misaligned). 132/2=66 leaves a 2-way write-group conflict, which on
-    // ds_write_b64 costs ~2 LDS-array cycles per instruction.
-    constexpr int STS = 128 + 4;
-    extern __shared__ char smem_raw[];
-    __bf16* Qlds = (__bf16*)smem_raw;          // [64 q][SQ] (PI23 rows)
-    __bf16* dOl = Qlds + 64 * SQ;              // [64 q][SQ] (PI23 rows)
-    __bf16* dSTl = dOl + 64 * SQ;              // [64 q][STS] (dS^T, PI23 rows)
-    __bf16* PTl = dSTl + 64 * STS;             // [64 q][STS] (P^T, PI23 rows)
+    constexpr int SQ = FaDkvLds<DPAD>::S;      // image stride
+    extern __shared__ char smem_raw[];         // FaDkvLds<DPAD>::bytes(DROPOUT)
+    __bf16* Qlds = (__bf16*)smem_raw;          // [64 q][SQ]
+    __bf16* dOl = Qlds + 64 * SQ;              // [64 q][SQ]
+    float* Lsel = (float*)(dOl + 64 * SQ);     // [64 q] lse * log2(e)
+    float* NDel = Lsel + 64;                   // [64 q] -delta
+    uint32_t* Rw = (uint32_t*)(NDel + 64);     // [64 q] row words (DROPOUT only)
 
     const int kend = min(L, ks + 128);
 
+    // this wave's K and V fragments (B-layout of K^T / V^T: j = lr -> key)
     const int krow = ks + wave * 16 + lr;
     const bool kvalid = krow < kend;
     bf16x8 kfr[KCH], vfr[KCH];
@@ -906,32 +933,20 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
         dkr[dc] = {0.f, 0.f, 0.f, 0.f};
     }
 
-    // dropout: here a lane owns 4 consecutive KEYS for the whole kernel, so
-    // the column words are the hoisted ones; row words are per q block
-    uint32_t drop_cw[4];
-    if constexpr (DROPOUT) {
-        const uint32_t drop_hw = drop_head_word(seed_hi, (uint32_t)h);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            drop_cw[r] = drop_col_word(drop_hw, (uint32_t)(s0 + ks + wave * 16 + lg * 4 + r));
-    }
+    // dropout: a lane owns ONE key for the whole kernel, so its column word
+    // is hoisted; the tile's 64 row words are mixed once per workgroup (Rw)
+    uint32_t drop_cw = 0;
+    if constexpr (DROPOUT)
+        drop_cw = drop_col_word(drop_head_word(seed_hi, (uint32_t)h), (uint32_t)(s0 + krow));
 
-    // lane base addresses for the dK/dV tr16 ladders
-    const int tr_jj = (lane >> 2) & 3;
-    const int tr_g8 = (lane >> 4) * 8;
-    const int tr_cc = (lane & 3) * 4;
-    // Two lane bases per image PAIR: dOl sits 64*SQ elements above Qlds and
-    // PTl 64*STS above dSTl — both displacements fit the 16-bit ds_read
-    // immediate, so the second image of each pair rides the offset field
-    // instead of holding two more address registers (dkv is register-bound).
-    const unsigned aQ0 = (unsigned)(size_t)(Qlds + PI23(tr_g8 + tr_jj) * SQ + tr_cc);
-    const unsigned aQ1 = (unsigned)(size_t)(Qlds + PI23(tr_g8 + 4 + tr_jj) * SQ + tr_cc);
-    const unsigned aDS0 = (unsigned)(size_t)(dSTl + PI23(tr_g8 + tr_jj) * STS + wave * 16 + tr_cc);
-    const unsigned aDS1 = (unsigned)(size_t)(dSTl + PI23(tr_g8 + 4 + tr_jj) * STS + wave * 16 + tr_cc);
+    // lane base addresses for the dK^T/dV^T tr16 ladders (permuted query
+    // order). One pair serves both images: dOl sits 64*SQ elements above
+    // Qlds, a displacement that fits the 16-bit ds_read immediate.
+    unsigned aQ0, aQ1;
+    fa_tr16_perm_bases(Qlds, SQ, lane, aQ0, aQ1);
     constexpr int DO_IMM = 64 * SQ * 2;        // dOl = Qlds + this (bytes)
-    constexpr int PT_IMM = 64 * STS * 2;       // PTl = dSTl + this (bytes)
-    static_assert(DO_IMM + 32 * SQ * 2 + 16 * 2 < 65536, "ds offset range");
-    static_assert(PT_IMM + 32 * STS * 2 + 16 * 2 < 65536, "ds offset range");
+    static_assert(DO_IMM + 32 * SQ * 2 + DPAD * 2 < 65536, "ds offset range");
+    const float scale2 = scale * DOL_LOG2E;
 
     // T5 static priority (guide §5.5): the later-dispatched half of an
     // 8-wave workgroup loses VALU arbitration to the older half; one
@@ -954,10 +969,107 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
             int qq = pidx / ((DPAD - D) / 8);
             int d0 = D + (pidx % ((DPAD - D) / 8)) * 8;
             bf16x8 z = {};
-            *(bf16x8*)&Qlds[PI23(qq) * SQ + d0] = z;
-            *(bf16x8*)&dOl[PI23(qq) * SQ + d0] = z;
+            *(bf16x8*)&Qlds[qq * SQ + d0] = z;
+            *(bf16x8*)&dOl[qq * SQ + d0] = z;
         }
     }
+
+    // One 32-query chunk c of the staged tile. Per 16-query block: S = Q*K^T
+    // and dP = dO*V^T MFMAs (element x is key = krow, query = qs + 16*cb +
+    // 4*lg + x), then that block's P and dS packed into half of the chunk's
+    // fragments — one C-pair live. Then dV^T += dO^T*P and dK^T += Q^T*dS
+    // through ONE depth-3 tr16 ladder over the dO image and then the Q
+    // image; the image and statistics reads above were consumed by the
+    // score MFMAs / the softmax, so no LDS op is outstanding when it opens.
+    auto dkv_chunk = [&](auto cc, const int qs, const int full) {
+        constexpr int c = decltype(cc)::value;
+        bf16x8 pf, dsf;
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) {
+            const int cb = 2 * c + hb;
+            // -delta: the dP chain's initial accumulator, or (dropout, where
+            // dP is masked first) an addend read after the chain
+            f32x4 st = {0.f, 0.f, 0.f, 0.f};
+            f32x4 dpt = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (!DROPOUT) dpt = *(const f32x4*)&NDel[cb * 16 + lg * 4];
+#pragma unroll
+            for (int kc = 0; kc < KCH; ++kc) {
+                int d0 = kc * 32 + lg * 8;
+                bf16x8 qa = *(const bf16x8*)&Qlds[(cb * 16 + lr) * SQ + d0];
+                st = MFMA16(qa, kfr[kc], st);
+                bf16x8 da = *(const bf16x8*)&dOl[(cb * 16 + lr) * SQ + d0];
+                dpt = MFMA16(da, vfr[kc], dpt);
+            }
+            const f32x4 ls = *(const f32x4*)&Lsel[cb * 16 + lg * 4];
+            u32x4 rw = {};
+            f32x4 nd = {};
+            if constexpr (DROPOUT) {
+                rw = *(const u32x4*)&Rw[cb * 16 + lg * 4];
+                nd = *(const f32x4*)&NDel[cb * 16 + lg * 4];
+            }
+            if (full) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    float pv = dkv_exp2(fmaf(st[x], scale2, -ls[x]));
+                    if constexpr (DROPOUT) {
+                        const bool keep = drop_keep_words(rw[x], drop_cw, drop_thr);
+                        pf[hb * 4 + x] = (__bf16)(keep ? pv : 0.f);
+                        dsf[hb * 4 + x] = (__bf16)(pv * fmaf(keep ? dpt[x] : 0.f, drop_rp, nd[x]));
+                    } else {
+                        pf[hb * 4 + x] = (__bf16)pv;
+                        dsf[hb * 4 + x] = (__bf16)(pv * dpt[x]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    const int qpos = qs + cb * 16 + lg * 4 + x;
+                    const bool ok = kvalid && qpos < L && krow <= qpos;
+                    float pv = ok ? dkv_exp2(fmaf(st[x], scale2, -ls[x])) : 0.f;
+                    if constexpr (DROPOUT) {
+                        const bool keep = drop_keep_words(rw[x], drop_cw, drop_thr);
+                        float ds = ok ? pv * fmaf(keep ? dpt[x] : 0.f, drop_rp, nd[x]) : 0.f;
+                        pf[hb * 4 + x] = (__bf16)(keep ? pv : 0.f);
+                        dsf[hb * 4 + x] = (__bf16)ds;
+                    } else {
+                        float ds = ok ? pv * dpt[x] : 0.f;
+                        pf[hb * 4 + x] = (__bf16)pv;
+                        dsf[hb * 4 + x] = (__bf16)ds;
+                    }
+                }
+            }
+        }
+
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int CB = c * 32 * SQ * 2;    // the chunk's 32 image rows (bytes)
+        bf16x4 alo[3], ahi[3];
+        tr16_issue<CB + DO_IMM>(aQ0, aQ1, alo[0], ahi[0]);
+        static_assert(DCH >= 2, "fragment 1 is the dO image's second 16-col block");
+        tr16_issue<CB + DO_IMM + 32>(aQ0, aQ1, alo[1], ahi[1]);
+#define DKV_STEP(i)                                                                                     \
+    if constexpr ((i) < 2 * DCH) {                                                                      \
+        constexpr int im_ = (i) / DCH, dc_ = (i) % DCH;                                                 \
+        if constexpr ((i) + 2 < 2 * DCH) {                                                              \
+            constexpr int in_ = ((i) + 2) / DCH, dn_ = ((i) + 2) % DCH;                                 \
+            tr16_issue<CB + (in_ ? 0 : DO_IMM) + dn_ * 32>(aQ0, aQ1, alo[((i) + 2) % 3], ahi[((i) + 2) % 3]); \
+            lgkm_wait2<4>(alo[(i) % 3], ahi[(i) % 3]);                                                  \
+        } else if constexpr ((i) + 1 < 2 * DCH) {                                                       \
+            lgkm_wait2<2>(alo[(i) % 3], ahi[(i) % 3]);                                                  \
+        } else {                                                                                        \
+            lgkm_wait2<0>(alo[(i) % 3], ahi[(i) % 3]);                                                  \
+        }                                                                                               \
+        if constexpr (im_ == 0)                                                                         \
+            dvr[dc_] = MFMA16(tr16_join8(alo[(i) % 3], ahi[(i) % 3]), pf, dvr[dc_]);                    \
+        else                                                                                            \
+            dkr[dc_] = MFMA16(tr16_join8(alo[(i) % 3], ahi[(i) % 3]), dsf, dkr[dc_]);                   \
+    }
+        DKV_STEP(0) DKV_STEP(1) DKV_STEP(2) DKV_STEP(3)
+        DKV_STEP(4) DKV_STEP(5) DKV_STEP(6) DKV_STEP(7)
+        DKV_STEP(8) DKV_STEP(9) DKV_STEP(10) DKV_STEP(11)
+        DKV_STEP(12) DKV_STEP(13) DKV_STEP(14) DKV_STEP(15)
+#undef DKV_STEP
+        __builtin_amdgcn_sched_barrier(0);
+    };
 
     // (hoisting the staging coordinates like dq/fwd costs 3 scratch
     // pointer reloads per iteration at dkv's 128-VGPR cap and measured
@@ -975,9 +1087,9 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
                 for (int pidx = threadIdx.x; pidx < 64 * D / 8; pidx += 512) {
                     int qq = (int)(((unsigned)pidx * st_magic) >> 22);
                     int d0 = (pidx - qq * (D / 8)) * 8;
-                    *(bf16x8*)&Qlds[PI23(qq) * SQ + d0] =
+                    *(bf16x8*)&Qlds[qq * SQ + d0] =
                         *(const bf16x8*)(q + (int64_t)(s0 + qs + qq) * q_ts + q_hoff + d0);
-                    *(bf16x8*)&dOl[PI23(qq) * SQ + d0] =
+                    *(bf16x8*)&dOl[qq * SQ + d0] =
                         *(const bf16x8*)(dout + (int64_t)(s0 + qs + qq) * do_ts + do_hoff + d0);
                 }
             } else {
@@ -986,132 +1098,36 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
                     int d0 = (pidx % (DPAD / 8)) * 8;
                     bool valid = (qs + qq) < L;
                     const __bf16* qp = q + (int64_t)(s0 + (valid ? qs + qq : 0)) * q_ts + q_hoff + d0;
-                    *(bf16x8*)&Qlds[PI23(qq) * SQ + d0] = load_bf16x8_guard(qp, d0, D, valid);
+                    *(bf16x8*)&Qlds[qq * SQ + d0] = load_bf16x8_guard(qp, d0, D, valid);
                     const __bf16* dp = dout + (int64_t)(s0 + (valid ? qs + qq : 0)) * do_ts + do_hoff + d0;
-                    *(bf16x8*)&dOl[PI23(qq) * SQ + d0] = load_bf16x8_guard(dp, d0, D, valid);
+                    *(bf16x8*)&dOl[qq * SQ + d0] = load_bf16x8_guard(dp, d0, D, valid);
                 }
+            }
+            // the tile's per-query statistics, one wave each; rows >= L are
+            // never read from memory and hold 0 (the mask drops them)
+            const int swave = __builtin_amdgcn_readfirstlane(wave);
+            const bool sok = qs + lane < L;
+            const int64_t sidx = (int64_t)h * T_total + s0 + (sok ? qs + lane : 0);
+            if (swave == 0) {
+                Lsel[lane] = sok ? lse[sidx] * DOL_LOG2E : 0.f;
+            } else if (swave == 1) {
+                NDel[lane] = sok ? -delta[sidx] : 0.f;
+            } else if (swave == 2) {
+                if constexpr (DROPOUT) Rw[lane] = drop_row_word(seed_lo, (uint32_t)(s0 + qs + lane));
             }
         }
         __syncthreads();
 
-        // Per q-column block: S^T = K*Q^T and dP^T = V*dO^T MFMAs, then that
-        // block's softmax straight into the LDS strips. Merging the two
-        // loops keeps only ONE C-fragment pair (8 VGPRs) live instead of
-        // four (32) — the register headroom the (512,4) cap needs.
         // The kernels are ISSUE-bound (SQ counters): the causal-mask
         // compare/select chain runs only on diagonal/edge tiles via a
-        // wave-uniform branch; ~94% of tiles take the maskless body.
-        const bool full_tile = (ks + wave * 16 + 16 <= qs + 1) && (kend == ks + 64) && (qs + 64 <= L);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            f32x4 st = {0.f, 0.f, 0.f, 0.f};
-            f32x4 dpt = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kc = 0; kc < KCH; ++kc) {
-                int d0 = kc * 32 + lg * 8;
-                bf16x8 qb = *(const bf16x8*)&Qlds[(cb * 16 + PI23(lr)) * SQ + d0];
-                st = MFMA16(kfr[kc], qb, st);
-                bf16x8 db = *(const bf16x8*)&dOl[(cb * 16 + PI23(lr)) * SQ + d0];
-                dpt = MFMA16(vfr[kc], db, dpt);
-            }
-            const int qpos = qs + cb * 16 + lr;
-            const bool qok = qpos < L;
-            float lsev = qok ? lse[(int64_t)h * T_total + s0 + qpos] * DOL_LOG2E : 0.f;
-            float delv = qok ? delta[(int64_t)h * T_total + s0 + qpos] : 0.f;
-            bf16x4 pvv, dsv;
-            uint32_t drop_rw = 0;
-            if constexpr (DROPOUT) drop_rw = drop_row_word(seed_lo, (uint32_t)(s0 + qpos));
-            if (__builtin_amdgcn_readfirstlane(full_tile ? 1 : 0)) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pv = exp2f(st[r] * (scale * DOL_LOG2E) - lsev);
-                    if constexpr (DROPOUT) {
-                        const bool keep = drop_keep_words(drop_rw, drop_cw[r], drop_thr);
-                        pvv[r] = (__bf16)(keep ? pv : 0.f);
-                        dsv[r] = (__bf16)(pv * ((keep ? dpt[r] * drop_rp : 0.f) - delv) * scale);
-                    } else {
-                        pvv[r] = (__bf16)pv;
-                        dsv[r] = (__bf16)(pv * (dpt[r] - delv) * scale);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int kpos = ks + wave * 16 + lg * 4 + r;
-                    bool ok = qok && kpos < kend && kpos <= qpos;
-                    float pv = ok ? exp2f(st[r] * (scale * DOL_LOG2E) - lsev) : 0.f;
-                    if constexpr (DROPOUT) {
-                        const bool keep = drop_keep_words(drop_rw, drop_cw[r], drop_thr);
-                        float ds = ok ? pv * ((keep ? dpt[r] * drop_rp : 0.f) - delv) * scale : 0.f;
-                        pvv[r] = (__bf16)(keep ? pv : 0.f);
-                        dsv[r] = (__bf16)ds;
-                    } else {
-                        float ds = ok ? pv * (dpt[r] - delv) * scale : 0.f;
-                        pvv[r] = (__bf16)pv;
-                        dsv[r] = (__bf16)ds;
-                    }
-                }
-            }
-            const int srow = PI23(cb * 16 + lr) * STS + wave * 16 + lg * 4;
-            *(bf16x4*)&PTl[srow] = pvv;
-            *(bf16x4*)&dSTl[srow] = dsv;
-        }
-
-        // dV += P^T*dO then dK += dS^T*Q (contraction over q) — TWO
-        // independent depth-3 tr16 ladders: dO feeds only dV and Q only dK,
-        // so splitting halves the live A-fragment registers (one strip pair
-        // instead of two) and the freed budget funds a third in-flight
-        // fragment — one MFMA per wait no longer exposes LDS latency.
-        {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // exact counts from here
-            __builtin_amdgcn_sched_barrier(0);
-            bf16x4 a_lo[2], a_hi[2];
-            tr16_issue<PT_IMM>(aDS0, aDS1, a_lo[0], a_hi[0]);
-            tr16_issue<PT_IMM + 32 * STS * 2>(aDS0, aDS1, a_lo[1], a_hi[1]);
-            bf16x4 blo[3], bhi[3];
-            tr16_issue<DO_IMM>(aQ0, aQ1, blo[0], bhi[0]);
-            tr16_issue<DO_IMM + ((1 / DCH) * 32 * SQ + (1 % DCH) * 16) * 2>(aQ0, aQ1, blo[1], bhi[1]);
-            lgkm_wait4<4>(a_lo[0], a_hi[0], a_lo[1], a_hi[1]);
-            bf16x8 af0 = tr16_join8(a_lo[0], a_hi[0]);
-            bf16x8 af1 = tr16_join8(a_lo[1], a_hi[1]);
-#define DKV_HALF(i, IMM, ACC, AF0, AF1)                                                                 \
-    if constexpr ((i) < 2 * DCH) {                                                                      \
-        constexpr int kc2_ = (i) / DCH, dc_ = (i) % DCH;                                                \
-        if constexpr ((i) + 2 < 2 * DCH) {                                                              \
-            constexpr int kn_ = ((i) + 2) / DCH, dn_ = ((i) + 2) % DCH;                                 \
-            tr16_issue<(kn_ * 32 * SQ + dn_ * 16) * 2 + (IMM)>(aQ0, aQ1, blo[((i) + 2) % 3], bhi[((i) + 2) % 3]); \
-            lgkm_wait2<4>(blo[(i) % 3], bhi[(i) % 3]);                                                  \
-        } else if constexpr ((i) + 1 < 2 * DCH) {                                                       \
-            lgkm_wait2<2>(blo[(i) % 3], bhi[(i) % 3]);                                                  \
-        } else {                                                                                        \
-            lgkm_wait2<0>(blo[(i) % 3], bhi[(i) % 3]);                                                  \
-        }                                                                                               \
-        ACC[dc_] = MFMA16(kc2_ ? (AF1) : (AF0), tr16_join8(blo[(i) % 3], bhi[(i) % 3]), ACC[dc_]);      \
-    }
-#define DKV_A(i) DKV_HALF(i, DO_IMM, dvr, af0, af1)
-            DKV_A(0) DKV_A(1) DKV_A(2) DKV_A(3)
-            DKV_A(4) DKV_A(5) DKV_A(6) DKV_A(7)
-            DKV_A(8) DKV_A(9) DKV_A(10) DKV_A(11)
-            DKV_A(12) DKV_A(13) DKV_A(14) DKV_A(15)
-#undef DKV_A
-            // half B: dK += dS^T * Q. The strip A-fragments and the first
-            // two Q B-fragments are issued, then one counted wait.
-            tr16_issue<0>(aDS0, aDS1, a_lo[0], a_hi[0]);
-            tr16_issue<32 * STS * 2>(aDS0, aDS1, a_lo[1], a_hi[1]);
-            tr16_issue<0>(aQ0, aQ1, blo[0], bhi[0]);
-            tr16_issue<((1 / DCH) * 32 * SQ + (1 % DCH) * 16) * 2>(aQ0, aQ1, blo[1], bhi[1]);
-            lgkm_wait4<4>(a_lo[0], a_hi[0], a_lo[1], a_hi[1]);
-            af0 = tr16_join8(a_lo[0], a_hi[0]);
-            af1 = tr16_join8(a_lo[1], a_hi[1]);
-#define DKV_B(i) DKV_HALF(i, 0, dkr, af0, af1)
-            DKV_B(0) DKV_B(1) DKV_B(2) DKV_B(3)
-            DKV_B(4) DKV_B(5) DKV_B(6) DKV_B(7)
-            DKV_B(8) DKV_B(9) DKV_B(10) DKV_B(11)
-            DKV_B(12) DKV_B(13) DKV_B(14) DKV_B(15)
-#undef DKV_B
-#undef DKV_HALF
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        // wave-uniform branch: a wave takes the maskless body when its 16
+        // keys lie inside the strip, none is above the tile's first query
+        // and the 64-query tile is interior (at L = 4096 every tile but
+        // the strip's own two diagonal ones).
+        const bool full_tile = (ks + wave * 16 + 16 <= qs + 1) && (ks + wave * 16 + 16 <= kend) && (qs + 64 <= L);
+        const int full = __builtin_amdgcn_readfirstlane(full_tile ? 1 : 0);
+        dkv_chunk(std::integral_constant<int, 0>{}, qs, full);
+        dkv_chunk(std::integral_constant<int, 1>{}, qs, full);
     }
 
     // Deterministic join: each (kv-tile, q-head) workgroup owns its keys'
@@ -1120,23 +1136,22 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     // reduces the G q-head contributions in a FIXED order. The round-1
     // fp32 atomicAdd join was arrival-order nondeterministic, which made
     // bit-exact checkpoint resume a coin flip.
+    // A lane holds 4 consecutive head-dim elements of its key per block: one
+    // 16-byte store per buffer (D % 8 == 0, so a group is all inside D or
+    // all pad, and every (t, h) row starts 16-byte aligned).
+    const int64_t rowoff = ((int64_t)(s0 + (kvalid ? krow : 0)) * H + h) * D;
 #pragma unroll
     for (int dc = 0; dc < DCH; ++dc) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int kpos = ks + wave * 16 + lg * 4 + r;
-            const int d = dc * 16 + lr;
-            if (kpos < kend && d < D) {
-                int64_t idx = ((int64_t)(s0 + kpos) * H + h) * D + d;
-                // non-temporal: the 1.3 GB of fp32 partials per launch must
-                // not evict the XCD-resident Q/dO slices (PMC: dkv read
-                // traffic 3.6 GB/launch vs ~1.4 GB ideal with plain stores)
-                __builtin_nontemporal_store(dkr[dc][r], &dk_acc[idx]);
-                if constexpr (DROPOUT)
-                    __builtin_nontemporal_store(dvr[dc][r] * drop_rp, &dv_acc[idx]);
-                else
-                    __builtin_nontemporal_store(dvr[dc][r], &dv_acc[idx]);
-            }
+        const int d0 = dc * 16 + lg * 4;
+        if (kvalid && d0 < D) {
+            // non-temporal: the 1.3 GB of fp32 partials per launch must
+            // not evict the XCD-resident Q/dO slices (PMC: dkv read
+            // traffic 3.6 GB/launch vs ~1.4 GB ideal with plain stores)
+            f32x4 dkv4 = dkr[dc] * scale;
+            __builtin_nontemporal_store(dkv4, (f32x4*)&dk_acc[rowoff + d0]);
+            f32x4 dvv4 = dvr[dc];
+            if constexpr (DROPOUT) dvv4 *= drop_rp;
+            __builtin_nontemporal_store(dvv4, (f32x4*)&dv_acc[rowoff + d0]);
         }
     }
 }
@@ -1399,12 +1414,10 @@ static int launch_fa_bwd(hipStream_t stream, const __bf16* q, const __bf16* k, c
                          float p_drop, uint64_t seed) {
     dim3 block(512);
     dim3 grid(max_tiles, batch, H);
-    constexpr int SQ = DPAD + 16;
     const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
     const uint32_t thr = drop_threshold(p_drop);
     const float rp = 1.f / (1.f - p_drop);
-    size_t shmem_dkv = (size_t)(64 * (128 + 4) * 2 + 64 * SQ * 2) * sizeof(__bf16);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<DPAD, DROPOUT>), grid, block, shmem_dkv, stream,
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<DPAD, DROPOUT>), grid, block, FaDkvLds<DPAD>::bytes(DROPOUT), stream,
                        q, k, v, dout, lse, delta, dk_acc, dv_acc, seq_begin, seq_end, H, Hkv, D, G,
                        q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
                        seed_lo, seed_hi, thr, rp);

@@ -184,7 +184,9 @@ def read_tr16(addrs):
 
 def regfrag_images():
     """The K/V images of fa_fwd / fa_bwd_dq with P / dS kept in registers
-    (S^T = K*Q^T): stride DPAD+16, three access patterns per image —
+    (S^T = K*Q^T) — and, with key and query swapped, the Q/dO images of
+    fa_bwd_dkv (S = Q*K^T), which use the same geometry and the same three
+    lane->address maps: stride DPAD+16, three access patterns per image —
     b128 staging writes, b128 row reads (score MFMAs) and the tr16 reads of
     the second product in PERMUTED key order (read h of 32-key chunk c takes
     row 32c + 16h + 4*(l>>4) + ((l>>2)&3), col d0 + 4*(l&3)). Natural row
