@@ -7,6 +7,7 @@ from .modeling import (
     GPTDolomiteForCausalLM,
     GPTDolomiteModel,
     GPTDolomitePreTrainedModel,
+    KVCache,
     ParameterizedEmbedding,
     ParameterizedLinear,
 )

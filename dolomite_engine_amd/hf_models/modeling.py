@@ -10,13 +10,16 @@ modeling_utils/attention/*). Three attention implementations:
     fused cross-entropy) behind the C-ABI in include/dolomite_hip.h.
   - "flash_attention_2" on a dense (B, S) batch (attention/flash.py): the
     same flash kernels in place on the padded buffer, one row span per
-    batch row — no (B, S, S) bias, no unpad / pad copies.
+    batch row — no (B, S, S) bias, no unpad / pad copies. This path also
+    generates: a preallocated KVCache, the single-token decode attention
+    kernel and GPTDolomiteForCausalLM.generate.
 
 Forward signature, list-input handling, loss semantics (boundary drops) and
 state-dict names match the reference exactly (drop-in boundary).
 """
 
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -26,9 +29,11 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from ..ops import (
     QKVLayout,
+    decode_attention,
     fused_cross_entropy,
     fused_layernorm,
     fused_rmsnorm,
+    kv_cache_append,
     rope_packed_qkv,
     span_attention,
     varlen_attention,
@@ -239,6 +244,50 @@ def apply_rotary_dense(x, cos, sin):
 
 
 # ---------------------------------------------------------------------------
+# KV cache (dense flash_attention_2 path; inference)
+# ---------------------------------------------------------------------------
+
+
+class KVCache:
+    """Preallocated per-layer key/value storage for generation on the dense
+    flash_attention_2 path (the reference keeps a DynamicCache and
+    concatenates, attention/flash.py:42-43; here nothing is reallocated).
+
+    k[i], v[i]: (B, max_length, Hkv, D) in the model dtype, uninitialised —
+    only positions below `lengths` are ever read. lengths: (B,) int32 on the
+    device, the keys stored per sequence. next_position: (B,) int64 on the
+    device, the position id the next token of each sequence gets.
+    get_seq_length() is the longest sequence as a host int, tracked on the
+    host without a readback."""
+
+    def __init__(self, config: GPTDolomiteConfig, batch_size: int, max_length: int, dtype, device):
+        self.batch_size = int(batch_size)
+        self.max_length = int(max_length)
+        shape = (self.batch_size, self.max_length, config.num_key_value_heads, config.head_dim)
+        self.k = [torch.empty(shape, dtype=dtype, device=device) for _ in range(config.n_layer)]
+        self.v = [torch.empty(shape, dtype=dtype, device=device) for _ in range(config.n_layer)]
+        self.lengths = torch.zeros(self.batch_size, dtype=torch.int32, device=device)
+        self.next_position = torch.zeros(self.batch_size, dtype=torch.int64, device=device)
+        self._seq_length = 0
+
+    def get_seq_length(self) -> int:
+        return self._seq_length
+
+
+class _LayerKV(NamedTuple):
+    """What one attention layer needs of the cache for one forward: prefill
+    appends the spans at dst_pos = 0 (cache_len None); a decode step appends
+    one row per sequence at dst_pos = lengths and attends over cache_len =
+    lengths + 1 keys, at most max_len of them."""
+
+    k: torch.Tensor
+    v: torch.Tensor
+    dst_pos: torch.Tensor
+    cache_len: torch.Tensor | None
+    max_len: int
+
+
+# ---------------------------------------------------------------------------
 # Attention
 # ---------------------------------------------------------------------------
 
@@ -319,18 +368,28 @@ class Attention(nn.Module):
         return q, k, v
 
     # ---- dense flash_attention_2: the padded batch on the flash kernels ----
-    def forward_dense_flash(self, hidden_states, spans, rope_cos_sin):
+    def forward_dense_flash(self, hidden_states, spans, rope_cos_sin, kv: _LayerKV | None = None):
         """The reference's dense flash path (attention/flash.py:95-135) without
         its unpad / pad copies: the (B, S, row_len) c_attn output as
         (B*S, row_len) IS the packed layout, with sequence b on the rows
         spans = (seq_begin, seq_end, max_seqlen) name. Pad rows of the
-        attention output are zero (pad_input's semantics)."""
+        attention output are zero (pad_input's semantics). With a cache
+        (kv): prefill additionally copies the spans' RoPE'd K/V into it; a
+        decode step (S = 1, spans = one row each) appends its row and runs
+        the decode kernel over the cache in place of the causal kernels."""
         B, S, _ = hidden_states.shape
         seq_begin, seq_end, max_seqlen = spans
         qkv = self.c_attn(hidden_states.reshape(B * S, -1))  # (B*S, row_len)
         if self.position_embedding_type == "rope":
             cos, sin = rope_cos_sin  # (B*S, D) fp32
             qkv = rope_packed_qkv(qkv, cos, sin, self.layout)
+        if kv is not None:
+            kv_cache_append(qkv, self.layout, seq_begin, seq_end, kv.k, kv.v, kv.dst_pos, max_rows=max_seqlen)
+            if kv.cache_len is not None:
+                attn_output = decode_attention(
+                    qkv, self.layout, kv.k, kv.v, kv.cache_len, self.softmax_scale, kv.max_len
+                )
+                return self.resid_dropout(self.c_proj(attn_output.view(B, S, -1)))
         attn_output = span_attention(
             qkv, seq_begin, seq_end, max_seqlen, self.layout, self.softmax_scale,
             dropout_p=self.attn_pdrop if self.training else 0.0,
@@ -338,11 +397,12 @@ class Attention(nn.Module):
         attn_output = self.c_proj(attn_output.view(B, S, -1))
         return self.resid_dropout(attn_output)
 
-    def forward_dense(self, hidden_states, attention_bias, rope_cos_sin, implementation):
+    def forward_dense(self, hidden_states, attention_bias, rope_cos_sin, implementation, kv=None):
         if implementation == "flash_attention_2":
             # attention_bias carries the row spans here, rope_cos_sin the
             # (B*S, D) fp32 tables (GPTDolomiteModel.dense_flash_inputs)
-            return self.forward_dense_flash(hidden_states, attention_bias, rope_cos_sin)
+            return self.forward_dense_flash(hidden_states, attention_bias, rope_cos_sin, kv)
+        assert kv is None, "the KV cache runs on flash_attention_2 only"
         B, S, _ = hidden_states.shape
         H, Hkv, D = self.num_heads, self.num_key_value_heads, self.head_dim
         q, k, v = self._split_dense(self.c_attn(hidden_states))
@@ -471,9 +531,9 @@ class GPTDolomiteBlock(nn.Module):
             mlp_out = mlp_out * self.m_residual
         return mlp_out, s
 
-    def forward_dense(self, hidden_states, attention_bias, rope_cos_sin, implementation):
+    def forward_dense(self, hidden_states, attention_bias, rope_cos_sin, implementation, kv=None):
         y, _ = self.ln_1(hidden_states)
-        attn_out = self.attn.forward_dense(y, attention_bias, rope_cos_sin, implementation)
+        attn_out = self.attn.forward_dense(y, attention_bias, rope_cos_sin, implementation, kv)
         if self.m_residual is not None:
             attn_out = attn_out * self.m_residual
         hidden_states = attn_out + hidden_states
@@ -621,9 +681,23 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
         cu_seqlens=None,
         max_seqlen=None,
     ):
-        assert past_key_values is None and not use_cache, "KV cache is not implemented (training engine)"
         assert inputs_embeds is None, "inputs_embeds input is not implemented"
         assert not output_hidden_states, "output_hidden_states is not implemented"
+
+        if use_cache or past_key_values is not None:
+            if self._use_padding_free_transformer:
+                raise NotImplementedError("KV caching is not supported with padding_free transformer")
+            if self.attention_implementation != "flash_attention_2":
+                raise NotImplementedError(
+                    f"the KV cache is built on the dense flash_attention_2 path only; this model runs "
+                    f"'{self.attention_implementation}' (load it with attention_implementation=flash_attention_2)"
+                )
+            if self.training:
+                raise RuntimeError("use_cache=True is an inference path: call model.eval() first")
+            hidden_states, cache = self._forward_dense_cached(
+                input_ids, attention_mask, position_ids, token_type_ids, past_key_values
+            )
+            return BaseModelOutputWithPast(last_hidden_state=hidden_states, past_key_values=cache)
 
         if self._use_padding_free_transformer:
             hidden_states = self._forward_padding_free(input_ids, position_ids, token_type_ids, cu_seqlens, max_seqlen)
@@ -705,6 +779,92 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             pos = position_ids.reshape(-1)
             rope_cos_sin = (cos.to(dtype).float()[pos].contiguous(), sin.to(dtype).float()[pos].contiguous())
         return spans, rope_cos_sin
+
+    # ---- dense flash_attention_2 with a KV cache: prefill or one decode step ----
+    def _embed(self, input_ids, position_ids, token_type_ids):
+        hs = self.wte(input_ids)
+        if token_type_ids is not None:
+            hs = hs + self.wte(token_type_ids)
+        if self.position_embedding_type == "learned_absolute":
+            hs = hs + self.wpe(position_ids)
+        hs = self.drop(hs)
+        if self.m_emb is not None:
+            hs = hs * self.m_emb
+        return hs
+
+    def _forward_dense_cached(self, input_ids, attention_mask, position_ids, token_type_ids, cache):
+        """Prefill (cache absent or empty; any S, mask left- or right-padded
+        or None): today's span path, plus one kv_cache_append per layer.
+        Decode (cache non-empty; S == 1): append at dst_pos = lengths, then
+        decode_attention over lengths + 1 keys. position_ids of a decode
+        step default to cache.next_position, which continues whatever
+        positions the prefill used. Every length check is on the host-side
+        length, before anything is launched."""
+        B, S = input_ids.shape
+        device = input_ids.device
+        dtype = self.wte.weight.dtype
+        if cache is None:
+            cache = KVCache(self.config, B, self.config.n_positions, dtype, device)
+        if not isinstance(cache, KVCache):
+            raise TypeError(f"past_key_values must be a KVCache, got {type(cache).__name__}")
+        if cache.batch_size != B:
+            raise ValueError(f"the cache holds {cache.batch_size} sequences, the batch has {B}")
+        past = cache.get_seq_length()
+        if past + S > cache.max_length:
+            raise ValueError(
+                f"KV cache overflow: {past} cached + {S} new tokens exceed max_length = {cache.max_length}"
+            )
+
+        if past == 0:  # ---- prefill ----
+            if position_ids is None:
+                position_ids = torch.arange(S, dtype=torch.long, device=device).unsqueeze(0).expand(B, -1)
+            hs = self._embed(input_ids, position_ids, token_type_ids)
+            spans, rope_cos_sin = self.dense_flash_inputs(attention_mask, position_ids, B, S, device, hs.dtype)
+            seq_begin, seq_end, max_seqlen = spans
+            dst_pos = torch.zeros(B, dtype=torch.int32, device=device)
+            for i, block in enumerate(self.h):
+                kv = _LayerKV(cache.k[i], cache.v[i], dst_pos, None, 0)
+                hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
+            count = seq_end - seq_begin
+            cache.lengths.copy_(count)
+            # position id of each sequence's last real token + 1 (0 for an all-pad row)
+            last = (seq_end.long() - 1).clamp_(min=0)
+            cache.next_position = torch.where(
+                count > 0, position_ids.reshape(-1)[last].long() + 1, torch.zeros_like(last)
+            )
+            cache._seq_length = max_seqlen
+        else:  # ---- one decode step ----
+            if S != 1:
+                raise NotImplementedError(
+                    f"{S} new tokens on a non-empty KV cache (chunked prefill / speculative verify) "
+                    "is not built: decode one token per step"
+                )
+            if attention_mask is not None and tuple(attention_mask.shape) not in ((B, 1), (B, past + 1)):
+                raise ValueError(
+                    f"attention_mask of a decode step must be (B, 1) or (B, past + 1) = {(B, past + 1)}, "
+                    f"got {tuple(attention_mask.shape)}"
+                )
+            if position_ids is None:
+                position_ids = cache.next_position.unsqueeze(1)
+            elif tuple(position_ids.shape) != (B, 1):
+                raise ValueError(f"position_ids of a decode step must be (B, 1), got {tuple(position_ids.shape)}")
+            hs = self._embed(input_ids, position_ids, token_type_ids)
+            rope_cos_sin = None
+            if self.position_embedding_type == "rope":
+                cos, sin = self.rope(max(cache.max_length, self.rope.max_seq_len_cached), device)
+                pos = position_ids.reshape(-1)
+                rope_cos_sin = (cos.to(dtype).float()[pos].contiguous(), sin.to(dtype).float()[pos].contiguous())
+            rows = torch.arange(B, dtype=torch.int32, device=device)
+            spans = (rows, rows + 1, 1)
+            new_len = cache.lengths + 1
+            for i, block in enumerate(self.h):
+                kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + 1)
+                hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
+            cache.lengths = new_len
+            cache.next_position = position_ids.reshape(-1).long() + 1
+            cache._seq_length = past + 1
+        hs, _ = self.ln_f(hs)
+        return hs, cache
 
     # ---- dense eager/sdpa path ----
     def _forward_dense(self, input_ids, attention_mask, position_ids, token_type_ids):
@@ -859,7 +1019,89 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
 
         loss = self.get_autoregressive_language_modeling_loss(lm_logits, labels, cu_seqlens)
 
-        return CausalLMOutputWithPast(loss=loss, logits=lm_logits)
+        return CausalLMOutputWithPast(
+            loss=loss, logits=lm_logits, past_key_values=transformer_outputs.past_key_values
+        )
+
+    @staticmethod
+    def _next_tokens(logits, do_sample, temperature, top_k, top_p, generator):
+        """(B, V) logits -> (B,) token ids: argmax, or temperature / top-k /
+        top-p (nucleus) sampling through torch ops with `generator`."""
+        logits = logits.float()
+        if not do_sample:
+            return logits.argmax(dim=-1)
+        if temperature != 1.0:
+            logits = logits / temperature
+        if top_k is not None and top_k > 0:
+            kth = logits.topk(min(int(top_k), logits.shape[-1]), dim=-1).values[:, -1:]
+            logits = logits.masked_fill(logits < kth, float("-inf"))
+        if top_p is not None and top_p < 1.0:
+            sorted_logits, order = logits.sort(dim=-1, descending=True)
+            probs = sorted_logits.softmax(dim=-1)
+            # drop a token when the mass BEFORE it already reaches top_p (the first always stays)
+            drop = probs.cumsum(dim=-1) - probs >= top_p
+            logits = logits.masked_fill(torch.zeros_like(drop).scatter(-1, order, drop), float("-inf"))
+        return torch.multinomial(logits.softmax(dim=-1), 1, generator=generator).squeeze(-1)
+
+    @torch.no_grad()
+    def generate(
+        self,
+        input_ids,
+        attention_mask=None,
+        max_new_tokens: int = 20,
+        do_sample: bool = False,
+        temperature: float = 1.0,
+        top_k: int | None = None,
+        top_p: float | None = None,
+        eos_token_id: int | None = None,
+        pad_token_id: int | None = None,
+        generator: torch.Generator | None = None,
+    ):
+        """Greedy or sampled continuation of a padded (B, S) prompt batch on
+        the dense flash_attention_2 path: one prefill into a KVCache of
+        S + max_new_tokens, the LM head on each sequence's last real row only
+        (no (B, S, V) logits), then one decode step per token. attention_mask
+        may be left- or right-padded (one contiguous run per row) or None.
+        After a sequence emits eos_token_id its later tokens are pad_token_id
+        (default: eos); the loop stops when every sequence has finished (one
+        host readback per step). Returns (B, S + n) ids, prompt included; the
+        new tokens sit in columns S.. for either padding side.
+
+        This is a plain loop, deliberately NOT transformers' GenerationMixin:
+        the transformers-5 Cache contract is not implemented, KVCache is the
+        only cache type forward() accepts."""
+        if self._use_padding_free_transformer:
+            raise NotImplementedError("padding free transformer doesn't support generation")
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        B, S = input_ids.shape
+        device = input_ids.device
+        if pad_token_id is None:
+            pad_token_id = eos_token_id
+        cache = KVCache(self.config, B, S + max_new_tokens, self.transformer.wte.weight.dtype, device)
+        out = self.transformer(input_ids, past_key_values=cache, attention_mask=attention_mask, use_cache=True)
+        if attention_mask is None:
+            hidden = out.last_hidden_state[:, -1]
+        else:
+            last = S - 1 - (attention_mask.to(device) != 0).to(torch.int8).flip(-1).argmax(-1)
+            hidden = out.last_hidden_state[torch.arange(B, device=device), last]
+
+        finished = torch.zeros(B, dtype=torch.bool, device=device)
+        new_tokens = []
+        for step in range(max_new_tokens):
+            logits = self.get_lm_logits(hidden)
+            if self.m_width is not None:
+                logits = logits / self.m_width
+            nxt = self._next_tokens(logits, do_sample, temperature, top_k, top_p, generator)
+            if eos_token_id is not None:
+                nxt = torch.where(finished, torch.full_like(nxt, pad_token_id), nxt)
+                finished = finished | (nxt == eos_token_id)
+            new_tokens.append(nxt)
+            if step + 1 == max_new_tokens or (eos_token_id is not None and bool(finished.all())):
+                break
+            out = self.transformer(nxt.unsqueeze(1), past_key_values=cache, use_cache=True)
+            hidden = out.last_hidden_state[:, 0]
+        return torch.cat([input_ids, torch.stack(new_tokens, dim=1)], dim=1)
 
     def get_lm_logits(self, hidden_states):
         return (

@@ -202,7 +202,9 @@ class MoEDolomiteModel(GPTDolomiteModel):
     def forward(self, input_ids=None, past_key_values=None, attention_mask=None, token_type_ids=None,
                 position_ids=None, inputs_embeds=None, use_cache=None, output_hidden_states=None,
                 return_dict=None, cu_seqlens=None, max_seqlen=None, output_router_logits=False):
-        assert past_key_values is None and not use_cache, "KV cache is not implemented (training engine)"
+        assert past_key_values is None and not use_cache, (
+            "KV cache / generate() is built for GPTDolomite on flash_attention_2 only; MoEDolomite is out of scope"
+        )
         assert inputs_embeds is None and not output_hidden_states
 
         all_router_logits = () if output_router_logits else None

@@ -87,6 +87,23 @@ class ModelWrapper(nn.Module):
     def save_pretrained(self, path: str) -> None:
         self.model.save_pretrained(path, safe_serialization=True)
 
+    def generate(self, batch: dict, generate_kwargs: dict) -> tuple[torch.Tensor, list[int]]:
+        """Reference model_wrapper/base.py:110-136 minus the tokenizer: the
+        generated ids with the prompt trimmed, and the number of generated
+        tokens per sequence (non-eos tokens + 1 for the eos itself)."""
+        if self.use_padding_free_transformer:
+            raise NotImplementedError("padding free transformer doesn't support generation")
+        device = next(self.model.parameters()).device
+        batch = {k: v.to(device) for k, v in batch.items()}
+        eos_token_id = getattr(self, "eos_token_id", None)
+        if eos_token_id is None:
+            eos_token_id = self.config.eos_token_id
+        generated = self.model.generate(**batch, **generate_kwargs, eos_token_id=eos_token_id)
+        generated = generated[:, batch["input_ids"].shape[1] :]
+        # add 1 to also count the eos token among the generated tokens
+        num_generated_tokens = ((generated != eos_token_id).sum(dim=-1) + 1).tolist()
+        return generated, num_generated_tokens
+
 
 class ModelWrapperForPretraining(ModelWrapper):
     """Loss-external pretraining forward (model_wrapper/pretraining.py:89-229):

@@ -754,6 +754,146 @@ def span_attention(qkv, seq_begin, seq_end, max_seqlen, layout: QKVLayout, scale
 
 
 # ---------------------------------------------------------------------------
+# KV cache append + single-token decode attention (inference only)
+# ---------------------------------------------------------------------------
+
+DECODE_KEY_TILE = 64          # keys per wave step of the decode kernel
+_DECODE_TARGET_WORKGROUPS = 512  # 2 per CU of the MI355X's 256
+
+
+def _no_grad_inputs(name, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{name} is inference only (no backward): call it under torch.no_grad()")
+
+
+def _check_cache(layout: QKVLayout, k_cache, v_cache):
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[2:] != (layout.Hkv, layout.D):
+        raise ValueError(
+            f"k_cache / v_cache must both be (B, S_cap, Hkv={layout.Hkv}, D={layout.D}), "
+            f"got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}"
+        )
+    if k_cache.stride() != v_cache.stride() or k_cache.stride(3) != 1:
+        raise ValueError("k_cache and v_cache must share strides, with a unit stride on the head dim")
+
+
+def kv_cache_append(qkv, layout: QKVLayout, seq_begin, seq_end, k_cache, v_cache, dst_pos,
+                    max_rows: int | None = None):
+    """Copy the K and V slots of packed (RoPE'd) qkv rows into the cache, in
+    place: row seq_begin[b] + i of qkv (T, row_len) goes to cache position
+    dst_pos[b] + i of sequence b, for i in [0, seq_end[b] - seq_begin[b]).
+    k_cache / v_cache: (B, S_cap, Hkv, D) in qkv's dtype. A position >= S_cap
+    is skipped; nothing else in the cache is touched. seq_begin, seq_end,
+    dst_pos: (B,) int32 on qkv's device. max_rows bounds the longest span
+    (launch sizing on the GPU; default T). Serves the prefill (the span
+    arrays, dst_pos = 0) and the decode step (one row per sequence)."""
+    lo = layout
+    _no_grad_inputs("kv_cache_append", qkv, k_cache, v_cache)
+    _check_cache(lo, k_cache, v_cache)
+    B, S_cap = k_cache.shape[:2]
+    for name, t in (("seq_begin", seq_begin), ("seq_end", seq_end), ("dst_pos", dst_pos)):
+        if t.dtype != torch.int32 or t.shape != (B,):
+            raise TypeError(f"{name} must be an int32 tensor of shape ({B},)")
+    if qkv.dim() != 2 or qkv.shape[1] != lo.row_len or qkv.dtype != k_cache.dtype:
+        raise ValueError("qkv must be (T, row_len) in the cache dtype")
+    T = qkv.shape[0]
+    max_rows = T if max_rows is None else min(int(max_rows), T)
+    if qkv.is_cuda:
+        qkv = qkv.contiguous()
+        with hip.prof("kv_cache_append"):
+            hip.check(
+                hip.lib().dolomite_kv_cache_append(
+                    hip.stream(), hip.ptr(qkv), hip.ptr(seq_begin), hip.ptr(seq_end), hip.ptr(dst_pos),
+                    hip.ptr(k_cache), hip.ptr(v_cache), B, max_rows, lo.Hkv, lo.D, S_cap,
+                    lo.row_len, lo.k_off, lo.v_off, lo.kv_hstride,
+                    k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), hip.dt(qkv),
+                ),
+                "kv_cache_append",
+            )
+        return
+    _, k, v = lo.unpack_cpu(qkv)
+    for b, (s, e, p) in enumerate(zip(seq_begin.tolist(), seq_end.tolist(), dst_pos.tolist())):
+        n = min(e - s, max_rows, S_cap - p)
+        if n > 0:
+            k_cache[b, p : p + n] = k[s : s + n]
+            v_cache[b, p : p + n] = v[s : s + n]
+
+
+def decode_num_splits(batch: int, layout: QKVLayout, max_len: int) -> int:
+    """The split count decode_attention picks for num_splits=None."""
+    tiles = -(-max(int(max_len), 1) // DECODE_KEY_TILE)
+    base = max(batch, 1) * layout.Hkv * -(-layout.G // 32)
+    return max(1, min(-(-_DECODE_TARGET_WORKGROUPS // base), -(-tiles // 4)))
+
+
+def decode_attention(qkv, layout: QKVLayout, k_cache, v_cache, cache_len, scale: float, max_len: int,
+                     num_splits: int | None = None):
+    """Attention of ONE new token per sequence over its cached keys.
+    qkv: (B, row_len) packed rows of the new tokens (only the q slots are
+    read; their K/V are already in the cache). k_cache / v_cache:
+    (B, S_cap, Hkv, D). cache_len: (B,) int32, the valid keys of each
+    sequence including the new token. No causal mask: keys [0, cache_len[b])
+    are attended, everything behind them is ignored whatever it holds.
+    cache_len[b] == 0 gives a zero row. max_len: host upper bound on
+    cache_len, <= S_cap. Returns (B, H*D).
+
+    num_splits: workgroups along the keys (split-KV, combined in ascending
+    split order — bitwise reproducible). None picks
+        min(ceil(512 / (B * Hkv * ceil(G / 32))), ceil(ceil(max_len / 64) / 4))
+    (at least 1): enough splits for about two workgroups on each of the 256
+    CUs, but never less than four 64-key tiles (one per wave) in a split.
+    Inference only: no backward."""
+    lo = layout
+    _no_grad_inputs("decode_attention", qkv, k_cache, v_cache)
+    _check_cache(lo, k_cache, v_cache)
+    B, S_cap = k_cache.shape[:2]
+    if qkv.dim() != 2 or qkv.shape != (B, lo.row_len):
+        raise ValueError(f"qkv must be (B, row_len) = {(B, lo.row_len)}, got {tuple(qkv.shape)}")
+    if cache_len.dtype != torch.int32 or cache_len.shape != (B,):
+        raise TypeError(f"cache_len must be an int32 tensor of shape ({B},)")
+    max_len = int(max_len)
+    if not 0 <= max_len <= S_cap:
+        raise ValueError(f"max_len {max_len} outside [0, S_cap = {S_cap}]")
+    if not scale > 0:
+        raise ValueError("scale must be > 0")
+    nsplit = decode_num_splits(B, lo, max_len) if num_splits is None else int(num_splits)
+    if nsplit < 1:
+        raise ValueError("num_splits must be >= 1")
+    if qkv.is_cuda:
+        qkv = qkv.contiguous()
+        o = torch.empty(B, lo.H * lo.D, dtype=qkv.dtype, device=qkv.device)
+        scratch = None
+        if nsplit > 1:
+            n = hip.lib().dolomite_fa_decode_scratch_floats(B, lo.H, lo.D, nsplit)
+            scratch = torch.empty(n, dtype=torch.float32, device=qkv.device)
+        with hip.prof("fa_decode"):
+            hip.check(
+                hip.lib().dolomite_fa_decode(
+                    hip.stream(), hip.ptr(qkv), hip.ptr(k_cache), hip.ptr(v_cache), hip.ptr(o),
+                    hip.ptr(scratch), hip.ptr(cache_len), B, lo.H, lo.Hkv, lo.D, lo.G, max_len, nsplit,
+                    lo.row_len, lo.q_gstride,
+                    k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+                    v_cache.stride(0), v_cache.stride(1), v_cache.stride(2),
+                    float(scale), hip.dt(qkv),
+                ),
+                "fa_decode",
+            )
+        return o
+    # CPU restatement: fp32 math, one sequence at a time
+    q, _, _ = lo.unpack_cpu(qkv)
+    G = lo.H // lo.Hkv
+    o = torch.zeros(B, lo.H, lo.D, dtype=torch.float32)
+    for b, n in enumerate(cache_len.tolist()):
+        n = min(max(n, 0), max_len)
+        if n == 0:
+            continue
+        kb = k_cache[b, :n].float().repeat_interleave(G, dim=1)  # (n, H, D)
+        vb = v_cache[b, :n].float().repeat_interleave(G, dim=1)
+        sc = torch.einsum("hd,nhd->hn", q[b].float(), kb) * scale
+        o[b] = torch.einsum("hn,nhd->hd", torch.softmax(sc, dim=-1), vb)
+    return o.reshape(B, lo.H * lo.D).to(qkv.dtype)
+
+
+# ---------------------------------------------------------------------------
 # Fused cross entropy (mean over non-ignored rows)
 # ---------------------------------------------------------------------------
 

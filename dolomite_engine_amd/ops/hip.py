@@ -71,6 +71,17 @@ _SIGNATURES = {
     ),
     "dolomite_fa_zero_gap_rows": ([_p, _p, _i64, _p, _p, _i32, _i64], _i32),
     "dolomite_fa_dropout_mask_probe": ([_p, _p, _u64, _f32, _i32, _i64, _i32, _i64, _i32], _i32),
+    "dolomite_kv_cache_append": (
+        [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32],
+        _i32,
+    ),
+    "dolomite_fa_decode_scratch_floats": ([_i32, _i32, _i32, _i32], _i64),
+    "dolomite_fa_decode": (
+        [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
+        _i32,
+    ),
     "dolomite_fa_grad_finalize": ([_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32], _i32),
     "dolomite_ce_fwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),
     "dolomite_ce_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),

@@ -296,6 +296,86 @@ int dolomite_fa_dropout_mask_probe(dolomite_stream_t stream, uint8_t* out,
                                    uint64_t seed, float p_drop, int H,
                                    int64_t tq0, int nq, int64_t tk0, int nk);
 
+/* ------------------------------------------------------------------------
+ * KV cache and single-token decode attention (inference; the reference's
+ * dense flash path with a cache, attention/flash.py:42-43 and the
+ * query_length == 1 branch at :94-100). bf16 only.
+ *
+ * Cache layout, shared by both entry points (elements):
+ *   k_cache[b, s, j, d] = k_cache + b*bstride + s*tstride + j*hstride + d
+ * and the same strides for v_cache; the natural allocation is a contiguous
+ * (B, S_cap, Hkv, D) bf16 tensor each. The cache is never cleared: positions
+ * at and beyond a sequence's length hold whatever the allocation held.
+ *
+ * dolomite_kv_cache_append copies the K and V slots of packed (RoPE'd) qkv
+ * rows into the cache: row src_begin[b] + i, for i in
+ * [0, src_end[b] - src_begin[b]), goes to cache position dst_pos[b] + i of
+ * sequence b. A position >= S_cap (or < 0) is skipped, never written;
+ * nothing outside the named positions is touched. One kernel serves the
+ * prefill (the span arrays of dolomite_fa_spans_fwd, dst_pos = 0) and the
+ * decode step (one row per sequence).
+ *   qkv: (T, row_tstride) rows; K head j of a row at k_off + j*kv_hstride,
+ *     V head j at v_off + j*kv_hstride (the QKVLayout strides).
+ *   src_begin, src_end, dst_pos: (batch,) int32 device pointers,
+ *     0 <= src_begin[b] <= src_end[b] <= T.
+ *   max_rows: an upper bound on src_end[b] - src_begin[b] (grid sizing;
+ *     rows beyond it are not copied).
+ * 16-byte loads and stores: D and every stride / offset must be multiples
+ * of 8 elements and the pointers 16-byte aligned.
+ * Error codes: 9010 dtype != bf16, 9030 negative size (batch, max_rows,
+ * S_cap), Hkv <= 0 or batch > 65535, 9031 D or a stride not a positive
+ * multiple of 8.
+ * ---------------------------------------------------------------------- */
+int dolomite_kv_cache_append(dolomite_stream_t stream, const void* qkv,
+                             const int32_t* src_begin, const int32_t* src_end,
+                             const int32_t* dst_pos, void* k_cache, void* v_cache,
+                             int batch, int max_rows, int Hkv, int D, int S_cap,
+                             int64_t row_tstride, int64_t k_off, int64_t v_off, int64_t kv_hstride,
+                             int64_t cache_bstride, int64_t cache_tstride, int64_t cache_hstride,
+                             int dtype);
+
+/* dolomite_fa_decode: one query token per sequence against the cache.
+ *   q[b, h, d] = q + b*q_tstride + (h/G)*q_gstride + (h%G)*D + d  (the new
+ *     token's packed row, one row per sequence)
+ *   cache_len: (batch,) int32 device pointer, the number of valid keys of
+ *     each sequence INCLUDING the new token (the append has already run).
+ *     Values are clamped into [0, max_len].
+ *   max_len: an upper bound on cache_len, <= the cache capacity.
+ *   o: (batch, H*D) bf16 row-major contiguous.
+ * There is no causal mask: the key range [0, cache_len[b]) is the mask.
+ * Keys at and beyond cache_len[b] never influence the result, whatever
+ * that memory holds (NaN and Inf included). cache_len[b] == 0 gives an
+ * all-(+0) output row.
+ *
+ * Split-KV: the grid is (nsplit, batch, Hkv) — Hkv * ceil(G / 32) for
+ * G > 32. Split c owns keys [c*chunk, min((c+1)*chunk, cache_len[b])) with
+ * chunk = ceil(max_len / nsplit) rounded up to the 64-key tile; a split
+ * with no keys is legal and contributes nothing. The G query heads of a kv
+ * head share one pass over its K/V. With nsplit > 1 each workgroup stores
+ * fp32 partials (unnormalised O, row max, row sum) exclusively into
+ * `scratch` and a second kernel combines them in ascending split order: no
+ * atomics, bitwise reproducible for fixed arguments. The result for
+ * different nsplit differs by fp32 rounding of the join.
+ *   scratch: dolomite_fa_decode_scratch_floats(batch, H, D, nsplit) floats,
+ *     16-byte aligned, caller-owned (0 and may be NULL for nsplit == 1;
+ *     the query returns -1 for invalid arguments). nsplit == 1 stores o
+ *     directly.
+ * Error codes: 9010 dtype != bf16, 9011 D > 128, 9015 scale not > 0, 9031
+ * D not a positive multiple of 8, 9032 negative / inconsistent sizes
+ * (H != Hkv*G included), 9033 nsplit < 1 or a grid dimension over 65535,
+ * 9034 nsplit > 1 without scratch.
+ * ---------------------------------------------------------------------- */
+int64_t dolomite_fa_decode_scratch_floats(int batch, int H, int D, int nsplit);
+int dolomite_fa_decode(dolomite_stream_t stream,
+                       const void* q, const void* k_cache, const void* v_cache, void* o,
+                       float* scratch, const int32_t* cache_len,
+                       int batch, int H, int Hkv, int D, int G,
+                       int max_len, int nsplit,
+                       int64_t q_tstride, int64_t q_gstride,
+                       int64_t k_bstride, int64_t k_tstride, int64_t k_hstride,
+                       int64_t v_bstride, int64_t v_tstride, int64_t v_hstride,
+                       float scale, int dtype);
+
 /* MFMA fragment-layout self-test: computes C = A(16x32) @ B(32x16) with the
  * compiled fragment mapping; host verifies against a CPU matmul.
  * A/B bf16 row-major contiguous, C fp32 row-major. */
