@@ -1021,6 +1021,9 @@ class GroupedExpertGemm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, offsets, max_rows):
         E, N, K = weight.shape
+        # the kernels index weight as dense (E, N, K) and bias as dense (E, N)
+        weight = weight.contiguous()
+        bias = bias.contiguous() if bias is not None else None
         y = torch.empty(x.shape[0], N, dtype=x.dtype, device=x.device)
         with hip.prof("moe_gemm_fwd"):
             hip.check(
@@ -1050,7 +1053,7 @@ class GroupedExpertGemm(torch.autograd.Function):
                 ),
                 "moe_gemm_dgrad",
             )
-        dw = torch.empty_like(weight)
+        dw = torch.empty(weight.shape, dtype=weight.dtype, device=weight.device)
         with hip.prof("moe_gemm_wgrad"):
             hip.check(
                 hip.lib().dolomite_moe_gemm_wgrad(
@@ -1119,11 +1122,15 @@ def _rows_combine(h, inv, batch_index, total_q, k_top):
 
 
 def grouped_expert_gemm(x, weight, bias, num_tokens_per_expert):
-    """Dispatch helper: HIP grouped kernel on CUDA bf16 with 8-aligned dims
-    (one launch for all experts); returns None if unsupported so the caller
-    can fall back to the eager per-expert loop."""
+    """Dispatch helper: HIP grouped kernel when x, weight and bias are all
+    CUDA bf16 and the dims 8-aligned (one launch for all experts); returns
+    None if unsupported so the caller can fall back to the eager per-expert
+    loop. weight and bias may be strided views: the kernels get dense copies."""
     E, N, K = weight.shape
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and K % 8 == 0 and N % 8 == 0):
+    tensors = (x, weight) if bias is None else (x, weight, bias)
+    if not all(t.is_cuda and t.dtype == torch.bfloat16 for t in tensors):
+        return None
+    if K % 8 != 0 or N % 8 != 0:
         return None
     # Measured crossover (tools_moe_gemm_probe.py, 1xMI355X): the one-launch
     # grouped kernel wins up to ~6x when per-expert GEMMs are small/launch-

@@ -377,7 +377,9 @@ def test_adamw_fused_clip_matches_explicit_scale():
 
 def test_moe_rows_combine_matches_index_add():
     """Deterministic top-k combine vs torch zeros+index_add (the reference
-    scatter-back, moe/base.py:127), plus bitwise run-to-run stability."""
+    scatter-back, moe/base.py:127) at a tolerance, plus bitwise run-to-run
+    stability. The bitwise check against the ordered fp32 sum is
+    tests/test_gpu_moe_kernels.py::test_rows_combine_bitwise."""
     from dolomite_engine_amd.ops.functional import _rows_combine
 
     g = torch.Generator().manual_seed(14)
@@ -399,7 +401,7 @@ def test_moe_rows_combine_matches_index_add():
     ref = torch.zeros(T, K, dtype=h.dtype, device=h.device).index_add(0, batch_index, h)
     # fp32-accumulated combine vs bf16 index_add: one rounding difference
     torch.testing.assert_close(out1, ref, rtol=1e-2, atol=1e-2)
-    # and exactly equals the fp32 reference rounded once
+    # and within one bf16 rounding (2^-8 relative) of the fp32 reference
     ref32 = torch.zeros(T, K, dtype=torch.float32, device=h.device).index_add(0, batch_index.cuda(), h.float())
     torch.testing.assert_close(out1.float(), ref32, rtol=4e-3, atol=4e-3)
 
