@@ -625,59 +625,86 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     }
 }
 
+// One causal-attention problem over the row spans [seq_begin[b], seq_end[b]),
+// as the six fa_varlen_* / fa_spans_* entry points receive it, in the order
+// the backward ones list it. The forward leaves dout .. dv_acc and do_ts
+// empty, the backward leaves o empty; lse is written by the forward and read
+// by the backward. The varlen entry points (back-to-back sequences) fill
+// (cu_seqlens, cu_seqlens + 1) and no p_drop (0: always valid).
+struct FaProblem {
+    dolomite_stream_t stream;
+    const void *q, *k, *v;
+    void* o;
+    const void* dout;
+    float* lse;
+    const float* delta;
+    void* dqkv_q;
+    float *dk_acc, *dv_acc;
+    const int32_t *seq_begin, *seq_end;
+    int batch, max_seqlen;
+    int64_t T;
+    int H, Hkv, D, G;
+    int64_t q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts;
+    float scale;
+    int dtype;
+    float p_drop;
+    uint64_t seed;
+    bool gaps;  // rows outside every span may exist (the fa_spans_* entry points)
+};
+
+// The entry points' argument checks, in their order of precedence; only the
+// forward checks the scale (its row max is taken before scaling).
+static int fa_check_args(const FaProblem& p, bool fwd) {
+    if (!drop_p_valid(p.p_drop)) return 9013;  // p_drop outside [0, 1) (NaN included)
+    if (p.dtype != DOLOMITE_BF16) return 9010;  // bf16 only (north-star dtype)
+    if (p.D > 128) return 9011;
+    if (fwd && !(p.scale > 0.f)) return 9015;
+    return 0;
+}
+
+// launch(integral_constant DPAD, bool_constant DROPOUT): the head dim rounded
+// up to a kernel instantiation; p_drop == 0 runs the DROPOUT=false ones (the
+// dropout-free code).
+template <typename Launch>
+static int fa_select_kernel(const FaProblem& p, Launch launch) {
+    auto by_dpad = [&](auto drop) {
+        if (p.D <= 32) return launch(std::integral_constant<int, 32>{}, drop);
+        if (p.D <= 64) return launch(std::integral_constant<int, 64>{}, drop);
+        if (p.D <= 96) return launch(std::integral_constant<int, 96>{}, drop);
+        return launch(std::integral_constant<int, 128>{}, drop);
+    };
+    return p.p_drop > 0.f ? by_dpad(std::true_type{}) : by_dpad(std::false_type{});
+}
+
+// grid.x = tiles of the longest sequence; shorter sequences' surplus
+// workgroups exit on the span-length check.
+static dim3 fa_grid(const FaProblem& p) { return dim3((p.max_seqlen + 127) / 128, p.batch, p.H); }
+
 template <int DPAD, bool DROPOUT>
-static int launch_fa_fwd(hipStream_t stream, const __bf16* q, const __bf16* k, const __bf16* v,
-                         __bf16* o, float* lse, const int32_t* seq_begin, const int32_t* seq_end,
-                         int batch, int64_t T, int H, int Hkv, int D, int G,
-                         int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs,
-                         int64_t v_ts, int64_t v_hs, int max_tiles, float scale,
-                         float p_drop, uint64_t seed) {
-    dim3 grid(max_tiles, batch, H), block(512);
-    hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT>), grid, block, FaKvLds<DPAD>::bytes(DROPOUT), stream,
-                       q, k, v, o, lse, seq_begin, seq_end, H, Hkv, D, G,
-                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, (int64_t)H * D, T, scale,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), drop_threshold(p_drop),
-                       1.f / (1.f - p_drop));
+static int launch_fa_fwd(const FaProblem& p) {
+    hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT>), fa_grid(p), dim3(512), FaKvLds<DPAD>::bytes(DROPOUT),
+                       (hipStream_t)p.stream, (const __bf16*)p.q, (const __bf16*)p.k, (const __bf16*)p.v,
+                       (__bf16*)p.o, p.lse, p.seq_begin, p.seq_end, p.H, p.Hkv, p.D, p.G,
+                       p.q_ts, p.q_gs, p.k_ts, p.k_hs, p.v_ts, p.v_hs, (int64_t)p.H * p.D, p.T, p.scale,
+                       (uint32_t)p.seed, (uint32_t)(p.seed >> 32), drop_threshold(p.p_drop),
+                       1.f / (1.f - p.p_drop));
     return dol_last_error();
 }
 
-// shared by every forward entry point; p_drop == 0 runs the DROPOUT=false
-// instantiations (the dropout-free code). Sequence b is rows
-// [seq_begin[b], seq_end[b]); the varlen entry points pass
-// (cu_seqlens, cu_seqlens + 1).
-static int fa_varlen_fwd_dispatch(dolomite_stream_t stream,
-                                  const void* q, const void* k, const void* v,
-                                  void* o, float* lse,
-                                  const int32_t* seq_begin, const int32_t* seq_end,
-                                  int batch, int max_seqlen, int64_t T,
-                                  int H, int Hkv, int D, int G,
-                                  int64_t q_tstride, int64_t q_gstride,
-                                  int64_t k_tstride, int64_t k_hstride,
-                                  int64_t v_tstride, int64_t v_hstride,
-                                  float scale, int dtype, float p_drop, uint64_t seed) {
-    if (dtype != DOLOMITE_BF16) return 9010;  // bf16 only (north-star dtype)
-    if (D > 128) return 9011;
-    if (!(scale > 0.f)) return 9015;  // the row max is taken before scaling
-    // grid.x = tiles of the longest sequence; shorter sequences' surplus
-    // workgroups exit on the span-length check.
-    int max_tiles = (max_seqlen + 127) / 128;
-    hipStream_t s = (hipStream_t)stream;
-#define CASE(DP, DROP)                                                                               \
-    return launch_fa_fwd<DP, DROP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,          \
-                                   (__bf16*)o, lse, seq_begin, seq_end, batch, T, H, Hkv, D, G, q_tstride, \
-                                   q_gstride, k_tstride, k_hstride, v_tstride, v_hstride, max_tiles, \
-                                   scale, p_drop, seed)
-    if (p_drop > 0.f) {
-        if (D <= 32) CASE(32, true);
-        if (D <= 64) CASE(64, true);
-        if (D <= 96) CASE(96, true);
-        CASE(128, true);
+// shared by every forward entry point
+static int fa_spans_fwd_dispatch(const FaProblem& p) {
+    int err = fa_check_args(p, true);
+    if (err) return err;
+    if (p.gaps) {
+        // o's gap rows (disjoint from every row the attention kernel stores)
+        err = dolomite_fa_zero_gap_rows(p.stream, p.o, (int64_t)p.H * p.D * (int64_t)sizeof(__bf16),
+                                        p.seq_begin, p.seq_end, p.batch, p.T);
+        if (err) return err;
+        if (p.batch == 0 || p.max_seqlen <= 0) return 0;  // every row is a gap row
     }
-    if (D <= 32) CASE(32, false);
-    if (D <= 64) CASE(64, false);
-    if (D <= 96) CASE(96, false);
-    CASE(128, false);
-#undef CASE
+    return fa_select_kernel(p, [&](auto dpad, auto drop) {
+        return launch_fa_fwd<decltype(dpad)::value, decltype(drop)::value>(p);
+    });
 }
 
 extern "C" int dolomite_fa_varlen_fwd(dolomite_stream_t stream,
@@ -689,9 +716,10 @@ extern "C" int dolomite_fa_varlen_fwd(dolomite_stream_t stream,
                                       int64_t k_tstride, int64_t k_hstride,
                                       int64_t v_tstride, int64_t v_hstride,
                                       float scale, int dtype) {
-    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T,
-                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
-                                  v_tstride, v_hstride, scale, dtype, 0.f, 0);
+    return fa_spans_fwd_dispatch({stream, q, k, v, o, nullptr, lse, nullptr, nullptr, nullptr, nullptr,
+                                  cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T, H, Hkv, D, G,
+                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride, 0,
+                                  scale, dtype, 0.f, 0, false});
 }
 
 extern "C" int dolomite_fa_varlen_fwd_dropout(dolomite_stream_t stream,
@@ -703,10 +731,10 @@ extern "C" int dolomite_fa_varlen_fwd_dropout(dolomite_stream_t stream,
                                               int64_t k_tstride, int64_t k_hstride,
                                               int64_t v_tstride, int64_t v_hstride,
                                               float scale, int dtype, float p_drop, uint64_t seed) {
-    if (!drop_p_valid(p_drop)) return 9013;  // p_drop outside [0, 1) (NaN included)
-    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T,
-                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
-                                  v_tstride, v_hstride, scale, dtype, p_drop, seed);
+    return fa_spans_fwd_dispatch({stream, q, k, v, o, nullptr, lse, nullptr, nullptr, nullptr, nullptr,
+                                  cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T, H, Hkv, D, G,
+                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride, 0,
+                                  scale, dtype, p_drop, seed, false});
 }
 
 // ===========================================================================
@@ -866,7 +894,7 @@ __device__ __forceinline__ float dkv_exp2(float x) { return __builtin_amdgcn_exp
 
 template <int DPAD>
 struct FaDkvLds {
-    static constexpr int S = DPAD + 16;
+    static constexpr int S = FaKvLds<DPAD>::S;  // the fwd / dq image stride
     static constexpr size_t image_bytes = (size_t)2 * 64 * S * sizeof(__bf16);  // multiple of 256
     static constexpr size_t bytes(bool dropout) {
         return image_bytes + 2 * 64 * sizeof(float) + (dropout ? 64 * sizeof(uint32_t) : 0);
@@ -1404,66 +1432,35 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
 }
 
 template <int DPAD, bool DROPOUT>
-static int launch_fa_bwd(hipStream_t stream, const __bf16* q, const __bf16* k, const __bf16* v,
-                         const __bf16* dout, const float* lse, const float* delta,
-                         __bf16* dqkv_q, float* dk_acc, float* dv_acc,
-                         const int32_t* seq_begin, const int32_t* seq_end,
-                         int batch, int64_t T, int H, int Hkv, int D, int G,
-                         int64_t q_ts, int64_t q_gs, int64_t k_ts, int64_t k_hs,
-                         int64_t v_ts, int64_t v_hs, int64_t do_ts, int max_tiles, float scale,
-                         float p_drop, uint64_t seed) {
-    dim3 block(512);
-    dim3 grid(max_tiles, batch, H);
-    const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
-    const uint32_t thr = drop_threshold(p_drop);
-    const float rp = 1.f / (1.f - p_drop);
+static int launch_fa_bwd(const FaProblem& p) {
+    const dim3 grid = fa_grid(p), block(512);
+    const hipStream_t stream = (hipStream_t)p.stream;
+    const __bf16 *q = (const __bf16*)p.q, *k = (const __bf16*)p.k, *v = (const __bf16*)p.v;
+    const __bf16* dout = (const __bf16*)p.dout;
+    const uint32_t seed_lo = (uint32_t)p.seed, seed_hi = (uint32_t)(p.seed >> 32);
+    const uint32_t thr = drop_threshold(p.p_drop);
+    const float rp = 1.f / (1.f - p.p_drop);
     hipLaunchKernelGGL((fa_bwd_dkv_kernel<DPAD, DROPOUT>), grid, block, FaDkvLds<DPAD>::bytes(DROPOUT), stream,
-                       q, k, v, dout, lse, delta, dk_acc, dv_acc, seq_begin, seq_end, H, Hkv, D, G,
-                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
-                       seed_lo, seed_hi, thr, rp);
+                       q, k, v, dout, p.lse, p.delta, p.dk_acc, p.dv_acc, p.seq_begin, p.seq_end,
+                       p.H, p.Hkv, p.D, p.G, p.q_ts, p.q_gs, p.k_ts, p.k_hs, p.v_ts, p.v_hs, p.do_ts,
+                       p.T, p.scale, seed_lo, seed_hi, thr, rp);
     int err = dol_last_error();
     if (err) return err;
     hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD, DROPOUT>), grid, block, FaKvLds<DPAD>::bytes(DROPOUT), stream,
-                       q, k, v, dout, lse, delta, dqkv_q, seq_begin, seq_end, H, Hkv, D, G,
-                       q_ts, q_gs, k_ts, k_hs, v_ts, v_hs, do_ts, T, scale,
-                       seed_lo, seed_hi, thr, rp);
+                       q, k, v, dout, p.lse, p.delta, (__bf16*)p.dqkv_q, p.seq_begin, p.seq_end,
+                       p.H, p.Hkv, p.D, p.G, p.q_ts, p.q_gs, p.k_ts, p.k_hs, p.v_ts, p.v_hs, p.do_ts,
+                       p.T, p.scale, seed_lo, seed_hi, thr, rp);
     return dol_last_error();
 }
 
-// shared by every backward entry point (see fa_varlen_fwd_dispatch)
-static int fa_varlen_bwd_dispatch(dolomite_stream_t stream,
-                                  const void* q, const void* k, const void* v,
-                                  const void* dout, const float* lse,
-                                  const float* delta, void* dqkv_q, float* dk_acc, float* dv_acc,
-                                  const int32_t* seq_begin, const int32_t* seq_end,
-                                  int batch, int max_seqlen, int64_t T,
-                                  int H, int Hkv, int D, int G,
-                                  int64_t q_tstride, int64_t q_gstride,
-                                  int64_t k_tstride, int64_t k_hstride,
-                                  int64_t v_tstride, int64_t v_hstride,
-                                  int64_t do_tstride,
-                                  float scale, int dtype, float p_drop, uint64_t seed) {
-    if (dtype != DOLOMITE_BF16) return 9010;
-    if (D > 128) return 9011;
-    int max_tiles = (max_seqlen + 127) / 128;
-    hipStream_t s = (hipStream_t)stream;
-#define CASE(DP, DROP)                                                                                  \
-    return launch_fa_bwd<DP, DROP>(s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,             \
-                                   (const __bf16*)dout, lse, delta, (__bf16*)dqkv_q, dk_acc, dv_acc,    \
-                                   seq_begin, seq_end, batch, T, H, Hkv, D, G, q_tstride, q_gstride, k_tstride, \
-                                   k_hstride, v_tstride, v_hstride, do_tstride, max_tiles, scale,       \
-                                   p_drop, seed)
-    if (p_drop > 0.f) {
-        if (D <= 32) CASE(32, true);
-        if (D <= 64) CASE(64, true);
-        if (D <= 96) CASE(96, true);
-        CASE(128, true);
-    }
-    if (D <= 32) CASE(32, false);
-    if (D <= 64) CASE(64, false);
-    if (D <= 96) CASE(96, false);
-    CASE(128, false);
-#undef CASE
+// shared by every backward entry point
+static int fa_spans_bwd_dispatch(const FaProblem& p) {
+    int err = fa_check_args(p, false);
+    if (err) return err;
+    if (p.gaps && (p.batch == 0 || p.max_seqlen <= 0)) return 0;  // every row is a gap row
+    return fa_select_kernel(p, [&](auto dpad, auto drop) {
+        return launch_fa_bwd<decltype(dpad)::value, decltype(drop)::value>(p);
+    });
 }
 
 extern "C" int dolomite_fa_varlen_bwd(dolomite_stream_t stream,
@@ -1477,10 +1474,10 @@ extern "C" int dolomite_fa_varlen_bwd(dolomite_stream_t stream,
                                       int64_t v_tstride, int64_t v_hstride,
                                       int64_t do_tstride,
                                       float scale, int dtype) {
-    return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
-                                  cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T, H, Hkv, D, G,
-                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
-                                  do_tstride, scale, dtype, 0.f, 0);
+    return fa_spans_bwd_dispatch({stream, q, k, v, nullptr, dout, const_cast<float*>(lse), delta, dqkv_q,
+                                  dk_acc, dv_acc, cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T,
+                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
+                                  v_tstride, v_hstride, do_tstride, scale, dtype, 0.f, 0, false});
 }
 
 extern "C" int dolomite_fa_varlen_bwd_dropout(dolomite_stream_t stream,
@@ -1494,11 +1491,10 @@ extern "C" int dolomite_fa_varlen_bwd_dropout(dolomite_stream_t stream,
                                               int64_t v_tstride, int64_t v_hstride,
                                               int64_t do_tstride,
                                               float scale, int dtype, float p_drop, uint64_t seed) {
-    if (!drop_p_valid(p_drop)) return 9013;
-    return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
-                                  cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T, H, Hkv, D, G,
-                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
-                                  do_tstride, scale, dtype, p_drop, seed);
+    return fa_spans_bwd_dispatch({stream, q, k, v, nullptr, dout, const_cast<float*>(lse), delta, dqkv_q,
+                                  dk_acc, dv_acc, cu_seqlens, cu_seqlens + 1, batch, max_seqlen, T,
+                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
+                                  v_tstride, v_hstride, do_tstride, scale, dtype, p_drop, seed, false});
 }
 
 // ===========================================================================
@@ -1559,18 +1555,10 @@ extern "C" int dolomite_fa_spans_fwd(dolomite_stream_t stream,
                                      int64_t k_tstride, int64_t k_hstride,
                                      int64_t v_tstride, int64_t v_hstride,
                                      float scale, int dtype, float p_drop, uint64_t seed) {
-    if (!drop_p_valid(p_drop)) return 9013;
-    if (dtype != DOLOMITE_BF16) return 9010;
-    if (D > 128) return 9011;
-    if (!(scale > 0.f)) return 9015;
-    // o's gap rows (disjoint from every row the attention kernel stores)
-    int err = dolomite_fa_zero_gap_rows(stream, o, (int64_t)H * D * (int64_t)sizeof(__bf16),
-                                        seq_begin, seq_end, batch, T);
-    if (err) return err;
-    if (batch == 0 || max_seqlen <= 0) return 0;  // every row is a gap row
-    return fa_varlen_fwd_dispatch(stream, q, k, v, o, lse, seq_begin, seq_end, batch, max_seqlen, T,
-                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
-                                  v_tstride, v_hstride, scale, dtype, p_drop, seed);
+    return fa_spans_fwd_dispatch({stream, q, k, v, o, nullptr, lse, nullptr, nullptr, nullptr, nullptr,
+                                  seq_begin, seq_end, batch, max_seqlen, T, H, Hkv, D, G,
+                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride, 0,
+                                  scale, dtype, p_drop, seed, true});
 }
 
 extern "C" int dolomite_fa_spans_bwd(dolomite_stream_t stream,
@@ -1585,14 +1573,10 @@ extern "C" int dolomite_fa_spans_bwd(dolomite_stream_t stream,
                                      int64_t v_tstride, int64_t v_hstride,
                                      int64_t do_tstride,
                                      float scale, int dtype, float p_drop, uint64_t seed) {
-    if (!drop_p_valid(p_drop)) return 9013;
-    if (dtype != DOLOMITE_BF16) return 9010;
-    if (D > 128) return 9011;
-    if (batch == 0 || max_seqlen <= 0) return 0;  // every row is a gap row
-    return fa_varlen_bwd_dispatch(stream, q, k, v, dout, lse, delta, dqkv_q, dk_acc, dv_acc,
-                                  seq_begin, seq_end, batch, max_seqlen, T, H, Hkv, D, G,
-                                  q_tstride, q_gstride, k_tstride, k_hstride, v_tstride, v_hstride,
-                                  do_tstride, scale, dtype, p_drop, seed);
+    return fa_spans_bwd_dispatch({stream, q, k, v, nullptr, dout, const_cast<float*>(lse), delta, dqkv_q,
+                                  dk_acc, dv_acc, seq_begin, seq_end, batch, max_seqlen, T,
+                                  H, Hkv, D, G, q_tstride, q_gstride, k_tstride, k_hstride,
+                                  v_tstride, v_hstride, do_tstride, scale, dtype, p_drop, seed, true});
 }
 
 // Keep-mask probe: out[(h*nq + i)*nk + j] = keep(seed, h, tq0+i, tk0+j) as

@@ -54,6 +54,16 @@ class QKVLayout:
             return QKVLayout(H, 1, D, H, row_len, 0, H * D, 0, H * D + D)
         raise ValueError(attention_head_type)
 
+    def operands(self, qkv: torch.Tensor):
+        """The q, k, v pointers of the C-ABI: head 0 of each in qkv's row 0."""
+        return hip.ptr(qkv), hip.ptr(qkv, self.k_off), hip.ptr(qkv, self.v_off)
+
+    def strides(self, token_stride: int | None = None):
+        """The C-ABI's (q_tstride, q_gstride, k_tstride, k_hstride, v_tstride,
+        v_hstride); token_stride defaults to the dense row_len."""
+        ts = self.row_len if token_stride is None else token_stride
+        return ts, self.q_gstride, ts, self.kv_hstride, ts, self.kv_hstride
+
     def unpack_cpu(self, qkv: torch.Tensor):
         """CPU view/reshape of packed qkv -> q (T,H,D), k/v (T,Hkv,D)
         (copies where the reference needs a reshape too)."""
@@ -436,12 +446,6 @@ def _drop_scale(p: float) -> float:
     return float(one / (one - torch.tensor(float(p), dtype=torch.float32)))
 
 
-def _cu_spans(cu):
-    """cu_seqlens -> the (begins, ends) lists of back-to-back sequences."""
-    cul = cu.tolist()
-    return cul[:-1], cul[1:]
-
-
 def _attn_fwd_cpu(qkv, begins, ends, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
     """fp32-softmax causal attention + lse over the row spans
     [begins[i], ends[i]) of the packed qkv, CPU restatement of the kernel.
@@ -477,40 +481,67 @@ def _attn_fwd_cpu(qkv, begins, ends, scale, lo: QKVLayout, dropout_p: float = 0.
     return o, lse
 
 
-class VarlenAttention(torch.autograd.Function):
-    """Causal varlen attention, the flash_attn_varlen_func replacement
-    (padding_free.py:51-62). Input: packed qkv (T, row_len); output
-    o (T, H*D). LSE saved for the recompute backward."""
+def _span_lists(seq_begin, seq_end):
+    """SpanAttention's sequence bounds as (begins, ends) lists."""
+    if seq_end is None:  # seq_begin is cu_seqlens
+        cul = seq_begin.tolist()
+        return cul[:-1], cul[1:]
+    return seq_begin.tolist(), seq_end.tolist()
+
+
+def _span_abi(seq_begin, seq_end):
+    """SpanAttention's sequence bounds for the C-ABI: the entry points' family
+    (fa_<kind>_fwd / _bwd, the hip.prof region names too), the batch and the
+    bound pointers."""
+    if seq_end is None:  # seq_begin is cu_seqlens
+        return "varlen", seq_begin.shape[0] - 1, (hip.ptr(seq_begin),)
+    return "spans", seq_begin.shape[0], (hip.ptr(seq_begin), hip.ptr(seq_end))
+
+
+class SpanAttention(torch.autograd.Function):
+    """Causal attention over row spans of the packed qkv (T, row_len):
+    sequence b is rows [seq_begin[b], seq_end[b]). Output o (T, H*D); LSE
+    saved for the recompute backward. Two callers, one set of kernels:
+
+    seq_end=None, seq_begin = cu_seqlens (batch + 1,): back-to-back
+    sequences, the flash_attn_varlen_func replacement (padding_free.py:51-62).
+    Every row is in a span; the fa_varlen_* entry points.
+
+    seq_begin, seq_end (batch,): sequences that are NOT back to back — a
+    padded (B, S) batch viewed as B*S rows, run in place. The dense
+    flash_attention_2 replacement (attention/flash.py:95-135) without its
+    unpad / pad copies. Rows outside every span: o and dqkv are exactly zero
+    (pad_input's semantics), by a gap-zeroing launch per buffer; the
+    fa_spans_* entry points."""
 
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen: int, layout: QKVLayout, scale: float,
+    def forward(ctx, qkv, seq_begin, seq_end, max_seqlen: int, layout: QKVLayout, scale: float,
                 dropout_p: float = 0.0, seed: int = 0):
         lo = layout
         T = qkv.shape[0]
-        batch = cu_seqlens.shape[0] - 1
         dropout_p = float(dropout_p)
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         if qkv.is_cuda:
             qkv = qkv.contiguous()
             o = torch.empty(T, lo.H * lo.D, dtype=qkv.dtype, device=qkv.device)
             lse = torch.empty(lo.H, T, dtype=torch.float32, device=qkv.device)
-            args = (
-                hip.stream(),
-                hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
-                hip.ptr(o), hip.ptr(lse), hip.ptr(cu_seqlens),
-                batch, int(max_seqlen), T, lo.H, lo.Hkv, lo.D, lo.G,
-                lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
-                lo.row_len, lo.kv_hstride, float(scale), hip.dt(qkv),
-            )
-            with hip.prof("fa_varlen_fwd"):
-                if dropout_p > 0:
-                    hip.check(hip.lib().dolomite_fa_varlen_fwd_dropout(*args, dropout_p, seed),
-                              "fa_varlen_fwd_dropout")
-                else:
-                    hip.check(hip.lib().dolomite_fa_varlen_fwd(*args), "fa_varlen_fwd")
+            kind, batch, bounds = _span_abi(seq_begin, seq_end)
+            # the varlen entry point that takes (p_drop, seed); fa_spans_fwd
+            # zeroes o's gap rows itself
+            lib = hip.lib()
+            fwd = lib.dolomite_fa_varlen_fwd_dropout if seq_end is None else lib.dolomite_fa_spans_fwd
+            with hip.prof(f"fa_{kind}_fwd"):
+                hip.check(
+                    fwd(
+                        hip.stream(), *lo.operands(qkv), hip.ptr(o), hip.ptr(lse), *bounds,
+                        batch, int(max_seqlen), T, lo.H, lo.Hkv, lo.D, lo.G, *lo.strides(),
+                        float(scale), hip.dt(qkv), dropout_p, seed,
+                    ),
+                    f"fa_{kind}_fwd",
+                )
         else:
-            o, lse = _attn_fwd_cpu(qkv, *_cu_spans(cu_seqlens), scale, lo, dropout_p, seed)
-        ctx.save_for_backward(qkv, o, lse, cu_seqlens)
+            o, lse = _attn_fwd_cpu(qkv, *_span_lists(seq_begin, seq_end), scale, lo, dropout_p, seed)
+        ctx.save_for_backward(qkv, o, lse, seq_begin, seq_end)
         ctx.layout = lo
         ctx.scale = scale
         ctx.max_seqlen = int(max_seqlen)
@@ -520,10 +551,9 @@ class VarlenAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, o, lse, cu = ctx.saved_tensors
+        qkv, o, lse, seq_begin, seq_end = ctx.saved_tensors
         lo: QKVLayout = ctx.layout
         T = qkv.shape[0]
-        batch = cu.shape[0] - 1
         if qkv.is_cuda:
             dout = dout.contiguous()
             delta = torch.empty(lo.H, T, dtype=torch.float32, device=qkv.device)
@@ -534,26 +564,27 @@ class VarlenAttention(torch.autograd.Function):
                 ),
                 "fa_bwd_preprocess",
             )
-            # (T, H, D) per-q-head partials, written exclusively per
-            # workgroup (no zero-init needed, every valid slot is stored)
+            # (T, H, D) per-q-head partials. Span rows of the partials and of
+            # dqkv are stored exclusively by the kernels (no zero-init needed);
+            # gap rows are left as allocated, reduced as they are by the
+            # finalize, and zeroed in dqkv afterwards (no whole-buffer memset:
+            # the partials are the largest buffers of the step)
             dk_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
             dv_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
             dqkv = torch.empty_like(qkv)
-            args = (
-                hip.stream(),
-                hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
-                hip.ptr(dout), hip.ptr(lse), hip.ptr(delta), hip.ptr(dqkv),
-                hip.ptr(dk_acc), hip.ptr(dv_acc),
-                hip.ptr(cu), batch, ctx.max_seqlen, T, lo.H, lo.Hkv, lo.D, lo.G,
-                lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
-                lo.row_len, lo.kv_hstride, lo.H * lo.D, float(ctx.scale), hip.dt(qkv),
-            )
-            with hip.prof("fa_varlen_bwd"):
-                if ctx.dropout_p > 0:
-                    hip.check(hip.lib().dolomite_fa_varlen_bwd_dropout(*args, ctx.dropout_p, ctx.seed),
-                              "fa_varlen_bwd_dropout")
-                else:
-                    hip.check(hip.lib().dolomite_fa_varlen_bwd(*args), "fa_varlen_bwd")
+            kind, batch, bounds = _span_abi(seq_begin, seq_end)
+            lib = hip.lib()
+            bwd = lib.dolomite_fa_varlen_bwd_dropout if seq_end is None else lib.dolomite_fa_spans_bwd
+            with hip.prof(f"fa_{kind}_bwd"):
+                hip.check(
+                    bwd(
+                        hip.stream(), *lo.operands(qkv), hip.ptr(dout), hip.ptr(lse), hip.ptr(delta),
+                        hip.ptr(dqkv), hip.ptr(dk_acc), hip.ptr(dv_acc), *bounds,
+                        batch, ctx.max_seqlen, T, lo.H, lo.Hkv, lo.D, lo.G, *lo.strides(), lo.H * lo.D,
+                        float(ctx.scale), hip.dt(qkv), ctx.dropout_p, ctx.seed,
+                    ),
+                    f"fa_{kind}_bwd",
+                )
             hip.check(
                 hip.lib().dolomite_fa_grad_finalize(
                     hip.stream(), hip.ptr(dk_acc), hip.ptr(dv_acc), hip.ptr(dqkv),
@@ -562,13 +593,23 @@ class VarlenAttention(torch.autograd.Function):
                 ),
                 "fa_grad_finalize",
             )
-            return dqkv, None, None, None, None, None, None
+            if seq_end is not None:
+                with hip.prof("fa_zero_gap_rows"):
+                    hip.check(
+                        hip.lib().dolomite_fa_zero_gap_rows(
+                            hip.stream(), hip.ptr(dqkv), lo.row_len * dqkv.element_size(),
+                            *bounds, batch, T,
+                        ),
+                        "fa_zero_gap_rows",
+                    )
+            return dqkv, None, None, None, None, None, None, None
         # CPU: differentiate the CPU restatement with torch autograd
         qkv_l = qkv.detach().requires_grad_(True)
         with torch.enable_grad():
-            o2, _ = _attn_fwd_cpu_autograd(qkv_l, *_cu_spans(cu), ctx.scale, lo, ctx.dropout_p, ctx.seed)
+            o2, _ = _attn_fwd_cpu_autograd(qkv_l, *_span_lists(seq_begin, seq_end), ctx.scale, lo,
+                                           ctx.dropout_p, ctx.seed)
             (dqkv,) = torch.autograd.grad(o2, qkv_l, dout)
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 def _attn_fwd_cpu_autograd(qkv, begins, ends, scale, lo: QKVLayout, dropout_p: float = 0.0, seed: int = 0):
@@ -609,126 +650,25 @@ def _attn_fwd_cpu_autograd(qkv, begins, ends, scale, lo: QKVLayout, dropout_p: f
     return o, None
 
 
+def _dropout_args(dropout_p, seed):
+    """Validated (dropout_p, seed) of the attention wrappers; seed=None draws
+    one, and only for dropout_p > 0: the RNG stream of p = 0 runs is untouched."""
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
+    if dropout_p == 0.0:
+        return 0.0, 0
+    return dropout_p, draw_attention_dropout_seed() if seed is None else int(seed)
+
+
 def varlen_attention(qkv, cu_seqlens, max_seqlen, layout: QKVLayout, scale: float,
                      dropout_p: float = 0.0, seed: int | None = None):
     """Causal varlen attention on the packed qkv. dropout_p > 0 drops
     attention probabilities with the counter-based keep mask
     (attention_dropout_keep_mask); seed=None draws one from torch's default
     CPU generator (draw_attention_dropout_seed)."""
-    dropout_p = float(dropout_p)
-    if not 0.0 <= dropout_p < 1.0:
-        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
-    if dropout_p == 0.0:  # no draw: the RNG stream of p = 0 runs is untouched
-        return VarlenAttention.apply(qkv, cu_seqlens, int(max_seqlen), layout, scale, 0.0, 0)
-    if seed is None:
-        seed = draw_attention_dropout_seed()
-    return VarlenAttention.apply(qkv, cu_seqlens, int(max_seqlen), layout, scale, dropout_p, int(seed))
-
-
-class SpanAttention(torch.autograd.Function):
-    """Causal attention over sequences that are NOT back to back: sequence b
-    is rows [seq_begin[b], seq_end[b]) of the packed qkv (T, row_len) — a
-    padded (B, S) batch viewed as B*S rows, run in place. The dense
-    flash_attention_2 replacement (attention/flash.py:95-135) without its
-    unpad / pad copies. Rows outside every span: o and dqkv are exactly zero
-    (pad_input's semantics). Same kernels as VarlenAttention."""
-
-    @staticmethod
-    def forward(ctx, qkv, seq_begin, seq_end, max_seqlen: int, layout: QKVLayout, scale: float,
-                dropout_p: float = 0.0, seed: int = 0):
-        lo = layout
-        T = qkv.shape[0]
-        batch = seq_begin.shape[0]
-        dropout_p = float(dropout_p)
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        if qkv.is_cuda:
-            qkv = qkv.contiguous()
-            o = torch.empty(T, lo.H * lo.D, dtype=qkv.dtype, device=qkv.device)
-            lse = torch.empty(lo.H, T, dtype=torch.float32, device=qkv.device)
-            with hip.prof("fa_spans_fwd"):
-                hip.check(
-                    hip.lib().dolomite_fa_spans_fwd(
-                        hip.stream(),
-                        hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
-                        hip.ptr(o), hip.ptr(lse), hip.ptr(seq_begin), hip.ptr(seq_end),
-                        batch, int(max_seqlen), T, lo.H, lo.Hkv, lo.D, lo.G,
-                        lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
-                        lo.row_len, lo.kv_hstride, float(scale), hip.dt(qkv), dropout_p, seed,
-                    ),
-                    "fa_spans_fwd",
-                )
-        else:
-            o, lse = _attn_fwd_cpu(qkv, seq_begin.tolist(), seq_end.tolist(), scale, lo, dropout_p, seed)
-        ctx.save_for_backward(qkv, o, lse, seq_begin, seq_end)
-        ctx.layout = lo
-        ctx.scale = scale
-        ctx.max_seqlen = int(max_seqlen)
-        ctx.dropout_p = dropout_p
-        ctx.seed = seed
-        return o
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, o, lse, seq_begin, seq_end = ctx.saved_tensors
-        lo: QKVLayout = ctx.layout
-        T = qkv.shape[0]
-        batch = seq_begin.shape[0]
-        if qkv.is_cuda:
-            dout = dout.contiguous()
-            delta = torch.empty(lo.H, T, dtype=torch.float32, device=qkv.device)
-            hip.check(
-                hip.lib().dolomite_fa_bwd_preprocess(
-                    hip.stream(), hip.ptr(o), hip.ptr(dout), hip.ptr(delta),
-                    T, lo.H, lo.D, lo.H * lo.D, lo.H * lo.D, hip.dt(qkv),
-                ),
-                "fa_bwd_preprocess",
-            )
-            # span rows of the partials and of dqkv are stored exclusively by
-            # the kernels; gap rows are left as allocated, reduced as they are
-            # by the finalize, and zeroed in dqkv afterwards (no whole-buffer
-            # memset: the partials are the largest buffers of the step)
-            dk_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
-            dv_acc = torch.empty(T, lo.H, lo.D, dtype=torch.float32, device=qkv.device)
-            dqkv = torch.empty_like(qkv)
-            with hip.prof("fa_spans_bwd"):
-                hip.check(
-                    hip.lib().dolomite_fa_spans_bwd(
-                        hip.stream(),
-                        hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
-                        hip.ptr(dout), hip.ptr(lse), hip.ptr(delta), hip.ptr(dqkv),
-                        hip.ptr(dk_acc), hip.ptr(dv_acc),
-                        hip.ptr(seq_begin), hip.ptr(seq_end), batch, ctx.max_seqlen, T,
-                        lo.H, lo.Hkv, lo.D, lo.G,
-                        lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
-                        lo.row_len, lo.kv_hstride, lo.H * lo.D, float(ctx.scale), hip.dt(qkv),
-                        ctx.dropout_p, ctx.seed,
-                    ),
-                    "fa_spans_bwd",
-                )
-            hip.check(
-                hip.lib().dolomite_fa_grad_finalize(
-                    hip.stream(), hip.ptr(dk_acc), hip.ptr(dv_acc), hip.ptr(dqkv),
-                    T, lo.Hkv, lo.D, lo.G, lo.row_len,
-                    lo.k_off, lo.kv_hstride, lo.v_off, hip.dt(qkv),
-                ),
-                "fa_grad_finalize",
-            )
-            with hip.prof("fa_zero_gap_rows"):
-                hip.check(
-                    hip.lib().dolomite_fa_zero_gap_rows(
-                        hip.stream(), hip.ptr(dqkv), lo.row_len * dqkv.element_size(),
-                        hip.ptr(seq_begin), hip.ptr(seq_end), batch, T,
-                    ),
-                    "fa_zero_gap_rows",
-                )
-            return dqkv, None, None, None, None, None, None, None
-        # CPU: differentiate the CPU restatement with torch autograd
-        qkv_l = qkv.detach().requires_grad_(True)
-        with torch.enable_grad():
-            o2, _ = _attn_fwd_cpu_autograd(qkv_l, seq_begin.tolist(), seq_end.tolist(), ctx.scale, lo,
-                                           ctx.dropout_p, ctx.seed)
-            (dqkv,) = torch.autograd.grad(o2, qkv_l, dout)
-        return dqkv, None, None, None, None, None, None, None
+    return SpanAttention.apply(qkv, cu_seqlens, None, int(max_seqlen), layout, scale,
+                               *_dropout_args(dropout_p, seed))
 
 
 def span_attention(qkv, seq_begin, seq_end, max_seqlen, layout: QKVLayout, scale: float,
@@ -739,18 +679,12 @@ def span_attention(qkv, seq_begin, seq_end, max_seqlen, layout: QKVLayout, scale
     max_seqlen is the longest span. Output (T, H*D) with zeros on the rows
     outside every span. Dropout as in varlen_attention: the keep mask is a
     function of the global row indices of the buffer."""
-    dropout_p = float(dropout_p)
-    if not 0.0 <= dropout_p < 1.0:
-        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
+    dropout_p, seed = _dropout_args(dropout_p, seed)
     if seq_begin.shape != seq_end.shape or seq_begin.dim() != 1:
         raise ValueError("seq_begin and seq_end must be 1-D tensors of one length")
     if seq_begin.dtype != torch.int32 or seq_end.dtype != torch.int32:
         raise TypeError("seq_begin and seq_end must be int32")
-    if dropout_p == 0.0:  # no draw: the RNG stream of p = 0 runs is untouched
-        return SpanAttention.apply(qkv, seq_begin, seq_end, int(max_seqlen), layout, scale, 0.0, 0)
-    if seed is None:
-        seed = draw_attention_dropout_seed()
-    return SpanAttention.apply(qkv, seq_begin, seq_end, int(max_seqlen), layout, scale, dropout_p, int(seed))
+    return SpanAttention.apply(qkv, seq_begin, seq_end, int(max_seqlen), layout, scale, dropout_p, seed)
 
 
 # ---------------------------------------------------------------------------

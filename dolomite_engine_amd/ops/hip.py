@@ -36,39 +36,7 @@ _SIGNATURES = {
     "dolomite_layernorm_bwd": ([_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32], _i32),
     "dolomite_reduce_partials": ([_p, _p, _p, _i64, _i64], _i32),
     "dolomite_rope_qkv": ([_p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _i32], _i32),
-    "dolomite_fa_varlen_fwd": (
-        [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
-         _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
-        _i32,
-    ),
     "dolomite_fa_bwd_preprocess": ([_p, _p, _p, _p, _i64, _i32, _i32, _i64, _i64, _i32], _i32),
-    "dolomite_fa_varlen_bwd": (
-        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
-         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
-        _i32,
-    ),
-    # the two entry points above + (float p_drop, uint64_t seed)
-    "dolomite_fa_varlen_fwd_dropout": (
-        [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
-         _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
-        _i32,
-    ),
-    "dolomite_fa_varlen_bwd_dropout": (
-        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
-         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
-        _i32,
-    ),
-    # the *_dropout pair with (seq_begin, seq_end) in place of cu_seqlens
-    "dolomite_fa_spans_fwd": (
-        [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
-         _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
-        _i32,
-    ),
-    "dolomite_fa_spans_bwd": (
-        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
-         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _u64],
-        _i32,
-    ),
     "dolomite_fa_zero_gap_rows": ([_p, _p, _i64, _p, _p, _i32, _i64], _i32),
     "dolomite_fa_dropout_mask_probe": ([_p, _p, _u64, _f32, _i32, _i64, _i32, _i64, _i32], _i32),
     "dolomite_kv_cache_append": (
@@ -99,6 +67,30 @@ _SIGNATURES = {
     "dolomite_build_sample_idx_i64": ([_p, _p, _i32, _i32, _i64, _p, _i64], _i32),
     "dolomite_build_blending_indices": ([_p, _p, _p, _i32, _i64], _i32),
 }
+
+
+def _fa_signature(bwd: bool, spans: bool, dropout: bool):
+    """The six fa_varlen_* / fa_spans_* entry points share one argument list:
+    stream, q, k, v, <buffers>, <bounds>, batch, max_seqlen, T, H, Hkv, D, G,
+    the six q/k/v strides [, do_tstride], scale, dtype [, p_drop, seed]."""
+    head = [_p, _p, _p, _p]                      # stream, q, k, v
+    # o, lse | dout, lse, delta, dqkv_q, dk_acc, dv_acc
+    bufs = [_p] * (6 if bwd else 2)
+    bounds = [_p] * (2 if spans else 1)          # seq_begin, seq_end | cu_seqlens
+    dims = [_i32, _i32, _i64, _i32, _i32, _i32, _i32]
+    strides = [_i64] * (7 if bwd else 6)
+    tail = [_f32, _i32] + ([_f32, _u64] if dropout else [])
+    return head + bufs + bounds + dims + strides + tail, _i32
+
+
+_SIGNATURES.update({
+    "dolomite_fa_varlen_fwd": _fa_signature(bwd=False, spans=False, dropout=False),
+    "dolomite_fa_varlen_bwd": _fa_signature(bwd=True, spans=False, dropout=False),
+    "dolomite_fa_varlen_fwd_dropout": _fa_signature(bwd=False, spans=False, dropout=True),
+    "dolomite_fa_varlen_bwd_dropout": _fa_signature(bwd=True, spans=False, dropout=True),
+    "dolomite_fa_spans_fwd": _fa_signature(bwd=False, spans=True, dropout=True),
+    "dolomite_fa_spans_bwd": _fa_signature(bwd=True, spans=True, dropout=True),
+})
 
 
 def so_path() -> Path:

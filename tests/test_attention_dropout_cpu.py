@@ -86,7 +86,7 @@ def test_keep_mask_p0_keeps_all_and_is_pure():
 
 
 # ---------------------------------------------------------------------------
-# 2. CPU VarlenAttention with dropout vs an explicit fp32 computation
+# 2. CPU varlen_attention with dropout vs an explicit fp32 computation
 # ---------------------------------------------------------------------------
 
 

@@ -151,10 +151,9 @@ class _Abi:
         ts = lo.row_len
         hip.check(
             hip.lib().dolomite_fa_varlen_fwd(
-                hip.stream(), hip.ptr(self.qkv), hip.ptr(self.qkv, lo.k_off), hip.ptr(self.qkv, lo.v_off),
+                hip.stream(), *lo.operands(self.qkv),
                 hip.ptr(self.o), hip.ptr(self.lse), hip.ptr(self.cu), len(lens), max(lens), T,
-                H, lo.Hkv, D, lo.G, ts, lo.q_gstride, ts, lo.kv_hstride, ts, lo.kv_hstride,
-                scale, hip.BF16,
+                H, lo.Hkv, D, lo.G, *lo.strides(ts), scale, hip.BF16,
             ),
             "fa_varlen_fwd",
         )
@@ -173,11 +172,10 @@ class _Abi:
         dv_acc = torch.full((T + _TAIL, H, D), _SENT, dtype=torch.float32, device="cuda")
         hip.check(
             hip.lib().dolomite_fa_varlen_bwd(
-                hip.stream(), hip.ptr(self.qkv), hip.ptr(self.qkv, lo.k_off), hip.ptr(self.qkv, lo.v_off),
+                hip.stream(), *lo.operands(self.qkv),
                 hip.ptr(self.do), hip.ptr(self.lse), hip.ptr(self.delta), hip.ptr(dqkv),
                 hip.ptr(dk_acc), hip.ptr(dv_acc), hip.ptr(self.cu), len(self.lens), max(self.lens), T,
-                H, lo.Hkv, D, lo.G, ts, lo.q_gstride, ts, lo.kv_hstride, ts, lo.kv_hstride, H * D,
-                self.scale, hip.BF16,
+                H, lo.Hkv, D, lo.G, *lo.strides(ts), H * D, self.scale, hip.BF16,
             ),
             "fa_varlen_bwd",
         )

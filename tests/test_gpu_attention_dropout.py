@@ -58,17 +58,15 @@ def test_invalid_p_drop_is_a_host_side_error_code():
     for bad in (1.0, -0.25, float("nan")):
         assert hip.lib().dolomite_fa_dropout_mask_probe(hip.stream(), hip.ptr(mask), 1, bad, 1, 0, 4, 0, 4) == 9013
         assert hip.lib().dolomite_fa_varlen_fwd_dropout(
-            hip.stream(), hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
+            hip.stream(), *lo.operands(qkv),
             hip.ptr(o), hip.ptr(lse), hip.ptr(cu), 1, T, T, lo.H, lo.Hkv, lo.D, lo.G,
-            lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride, lo.row_len, lo.kv_hstride,
-            0.25, hip.BF16, bad, 1,
+            *lo.strides(), 0.25, hip.BF16, bad, 1,
         ) == 9013
         assert hip.lib().dolomite_fa_varlen_bwd_dropout(
-            hip.stream(), hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
+            hip.stream(), *lo.operands(qkv),
             hip.ptr(o), hip.ptr(lse), hip.ptr(delta), hip.ptr(dqkv), hip.ptr(acc), hip.ptr(acc),
             hip.ptr(cu), 1, T, T, lo.H, lo.Hkv, lo.D, lo.G,
-            lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride, lo.row_len, lo.kv_hstride,
-            lo.H * lo.D, 0.25, hip.BF16, bad, 1,
+            *lo.strides(), lo.H * lo.D, 0.25, hip.BF16, bad, 1,
         ) == 9013
     torch.cuda.synchronize()
 

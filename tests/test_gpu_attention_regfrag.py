@@ -138,13 +138,11 @@ def test_key_order_fwd_bwd(head_type, H, Hkv, D, c):
 
 
 def _fwd_abi(lo, qkv, cu, max_len, T, scale, o, lse, t_stride=None):
-    ts = lo.row_len if t_stride is None else t_stride
     hip.check(
         hip.lib().dolomite_fa_varlen_fwd(
-            hip.stream(), hip.ptr(qkv), hip.ptr(qkv, lo.k_off), hip.ptr(qkv, lo.v_off),
+            hip.stream(), *lo.operands(qkv),
             hip.ptr(o), hip.ptr(lse), hip.ptr(cu), cu.numel() - 1, max_len, T,
-            lo.H, lo.Hkv, lo.D, lo.G, ts, lo.q_gstride, ts, lo.kv_hstride, ts, lo.kv_hstride,
-            scale, hip.BF16,
+            lo.H, lo.Hkv, lo.D, lo.G, *lo.strides(t_stride), scale, hip.BF16,
         ),
         "fa_varlen_fwd",
     )
@@ -233,10 +231,10 @@ def test_epilogue_stores_stay_inside_rows_and_columns(head_type, H, Hkv, D, lens
     dv_acc = torch.empty(T, H, D, dtype=torch.float32, device="cuda")
     hip.check(
         hip.lib().dolomite_fa_varlen_bwd(
-            hip.stream(), hip.ptr(buf), hip.ptr(buf, lo.k_off), hip.ptr(buf, lo.v_off),
+            hip.stream(), *lo.operands(buf),
             hip.ptr(do_g), hip.ptr(lse), hip.ptr(delta), hip.ptr(dqkv), hip.ptr(dk_acc), hip.ptr(dv_acc),
             hip.ptr(cu_g), len(lens), max(lens), T, H, Hkv, D, lo.G,
-            ts, lo.q_gstride, ts, lo.kv_hstride, ts, lo.kv_hstride, H * D, scale, hip.BF16,
+            *lo.strides(ts), H * D, scale, hip.BF16,
         ),
         "fa_varlen_bwd",
     )

@@ -108,10 +108,9 @@ def test_gap_rows_are_zeroed_in_nan_prefilled_buffers(side):
     lse = torch.zeros(H, T, dtype=torch.float32, device="cuda")
     hip.check(
         hip.lib().dolomite_fa_spans_fwd(
-            hip.stream(), hip.ptr(x), hip.ptr(x, lo.k_off), hip.ptr(x, lo.v_off),
+            hip.stream(), *lo.operands(x),
             hip.ptr(o), hip.ptr(lse), hip.ptr(bg), hip.ptr(en), B, max(LENS), T,
-            lo.H, lo.Hkv, lo.D, lo.G, lo.row_len, lo.q_gstride, lo.row_len, lo.kv_hstride,
-            lo.row_len, lo.kv_hstride, 1.0 / math.sqrt(D), hip.BF16, 0.0, 0,
+            lo.H, lo.Hkv, lo.D, lo.G, *lo.strides(), 1.0 / math.sqrt(D), hip.BF16, 0.0, 0,
         ),
         "fa_spans_fwd",
     )

@@ -103,7 +103,7 @@ def main():
 
         cls.forward, cls.backward = staticmethod(fwd), staticmethod(bwd)
 
-    for cls, nm in [(F.VarlenAttention, "ATTN"), (F.RoPEPackedQKV, "ROPE"),
+    for cls, nm in [(F.SpanAttention, "ATTN"), (F.RoPEPackedQKV, "ROPE"),
                     (F.FusedRMSNorm, "NORM"), (F.FusedCrossEntropy, "CE")]:
         wrap_fn(cls, nm)
     for name, mod in wrapper.model.named_modules():
