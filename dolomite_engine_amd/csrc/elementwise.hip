@@ -18,6 +18,56 @@
 
 #include <math.h>
 
+#include <type_traits>
+
+// ===========================================================================
+// Host-side kernel selectors: each turns run-time arguments into the tags of
+// one kernel instantiation and calls fn with them once; fn launches and
+// returns the entry point's code. Every launch below goes through these, so
+// its argument list is written once, with casts to the selected T.
+// ===========================================================================
+
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// fn(std::true_type / std::false_type)
+template <typename Fn>
+static int select_bool(bool b, Fn fn) {
+    return b ? fn(std::true_type{}) : fn(std::false_type{});
+}
+
+// fn(T{}): uint16_t for DOLOMITE_BF16, float for any other dtype.
+template <typename Fn>
+static int select_dtype(int dtype, Fn fn) {
+    return dtype == DOLOMITE_BF16 ? fn(uint16_t{}) : fn(float{});
+}
+
+// fn(T{}, Int<V>{}): the 16-byte vector width (8 bf16 / 4 fp32) when the
+// extent n is a multiple of it, the scalar V=1 instantiation otherwise.
+template <typename Fn>
+static int select_dtype_vec(int dtype, int64_t n, Fn fn) {
+    return select_dtype(dtype, [&](auto t) {
+        constexpr int W = 16 / (int)sizeof(t);
+        return n % W == 0 ? fn(t, Int<W>{}) : fn(t, Int<1>{});
+    });
+}
+
+// fn(T{}, Int<V>{}, Int<ITMAX>{}) for a norm row of H elements: the smallest
+// ITMAX bucket covering the ceil(H / (64*V)) vectors each lane owns, or 9002
+// (without calling fn) for a row wider than 16 * 64 * V.
+template <typename Fn>
+static int select_norm(int dtype, int64_t H, Fn fn) {
+    return select_dtype_vec(dtype, H, [&](auto t, auto v) {
+        int it = ((int)H + 64 * v - 1) / (64 * v);
+        if (it <= 2) return fn(t, v, Int<2>{});
+        if (it <= 4) return fn(t, v, Int<4>{});
+        if (it <= 5) return fn(t, v, Int<5>{});
+        if (it <= 8) return fn(t, v, Int<8>{});
+        if (it <= 16) return fn(t, v, Int<16>{});
+        return 9002;
+    });
+}
+
 // ===========================================================================
 // RMSNorm / LayerNorm — wave-per-row, register-resident, no barriers.
 // HBM-bound: one coalesced read of the row into VGPRs, wave-shuffle
@@ -84,72 +134,21 @@ __global__ void __launch_bounds__(256) rmsnorm_fwd_kernel(
     }
 }
 
-// Dispatch helper: pick the smallest ITMAX covering H at vector width V.
-// Requires H % V == 0 (true for every transformer width on this path);
-// falls back to V=1 otherwise.
-#define DOL_NORM_DISPATCH(KERN, T_, V_, HAS_RES_, ...)                                   \
-    do {                                                                                 \
-        int it = ((int)H + 64 * (V_)-1) / (64 * (V_));                                   \
-        if (it <= 2)                                                                     \
-            hipLaunchKernelGGL((KERN<T_, V_, 2, HAS_RES_>), grid, block, 0, stream_, __VA_ARGS__); \
-        else if (it <= 4)                                                                \
-            hipLaunchKernelGGL((KERN<T_, V_, 4, HAS_RES_>), grid, block, 0, stream_, __VA_ARGS__); \
-        else if (it <= 5)                                                                \
-            hipLaunchKernelGGL((KERN<T_, V_, 5, HAS_RES_>), grid, block, 0, stream_, __VA_ARGS__); \
-        else if (it <= 8)                                                                \
-            hipLaunchKernelGGL((KERN<T_, V_, 8, HAS_RES_>), grid, block, 0, stream_, __VA_ARGS__); \
-        else if (it <= 16)                                                               \
-            hipLaunchKernelGGL((KERN<T_, V_, 16, HAS_RES_>), grid, block, 0, stream_, __VA_ARGS__); \
-        else                                                                             \
-            return 9002;                                                                 \
-    } while (0)
-
 extern "C" int dolomite_rmsnorm_fwd(dolomite_stream_t stream,
                                     const void* x, const void* res_in, const void* w,
                                     void* y, void* res_out, float* rstd,
                                     int64_t T_rows, int64_t H, float eps, int dtype) {
     if (T_rows == 0) return 0;
-    hipStream_t stream_ = (hipStream_t)stream;
     dim3 grid((uint32_t)((T_rows + 3) / 4)), block(256);
-    bool has_res = res_in != nullptr;
-    if (dtype == DOLOMITE_BF16 && H % 8 == 0) {
-        if (has_res)
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, uint16_t, 8, true,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w,
-                              (uint16_t*)y, (uint16_t*)res_out, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, uint16_t, 8, false,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w,
-                              (uint16_t*)y, (uint16_t*)res_out, rstd, T_rows, (int)H, eps);
-    } else if (dtype == DOLOMITE_BF16) {
-        if (has_res)
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, uint16_t, 1, true,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w,
-                              (uint16_t*)y, (uint16_t*)res_out, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, uint16_t, 1, false,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w,
-                              (uint16_t*)y, (uint16_t*)res_out, rstd, T_rows, (int)H, eps);
-    } else if (H % 4 == 0) {
-        if (has_res)
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, float, 4, true,
-                              (const float*)x, (const float*)res_in, (const float*)w,
-                              (float*)y, (float*)res_out, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, float, 4, false,
-                              (const float*)x, (const float*)res_in, (const float*)w,
-                              (float*)y, (float*)res_out, rstd, T_rows, (int)H, eps);
-    } else {
-        if (has_res)
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, float, 1, true,
-                              (const float*)x, (const float*)res_in, (const float*)w,
-                              (float*)y, (float*)res_out, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(rmsnorm_fwd_kernel, float, 1, false,
-                              (const float*)x, (const float*)res_in, (const float*)w,
-                              (float*)y, (float*)res_out, rstd, T_rows, (int)H, eps);
-    }
-    return dol_last_error();
+    return select_norm(dtype, H, [&](auto t, auto v, auto it) {
+        return select_bool(res_in != nullptr, [&](auto has_res) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((rmsnorm_fwd_kernel<T, v, it, has_res>), grid, block, 0, (hipStream_t)stream,
+                               (const T*)x, (const T*)res_in, (const T*)w, (T*)y, (T*)res_out, rstd,
+                               T_rows, (int)H, eps);
+            return dol_last_error();
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -271,49 +270,30 @@ __global__ void __launch_bounds__(256) norm_bwd_kernel(
     }
 }
 
+// shared by dolomite_rmsnorm_bwd (mean = nullptr) and dolomite_layernorm_bwd
+template <bool IS_LN>
+static int launch_norm_bwd(dolomite_stream_t stream, const void* dy, const void* s, const void* w,
+                           const float* mean, const float* rstd, void* dx, float* dw_partial,
+                           const void* dres, int64_t T_rows, int64_t H, int dtype) {
+    if (T_rows == 0) return 0;
+    dim3 grid(RMS_BWD_BLOCKS), block(256);
+    return select_norm(dtype, H, [&](auto t, auto v, auto it) {
+        return select_bool(dres != nullptr, [&](auto has_dres) {
+            using T = decltype(t);
+            constexpr int MODE = (IS_LN ? 1 : 0) | (has_dres ? 2 : 0);
+            hipLaunchKernelGGL((norm_bwd_kernel<T, v, it, MODE>), grid, block, 0, (hipStream_t)stream,
+                               (const T*)dy, (const T*)s, (const T*)w, mean, rstd, (T*)dx, dw_partial,
+                               (const T*)dres, T_rows, (int)H);
+            return dol_last_error();
+        });
+    });
+}
+
 extern "C" int dolomite_rmsnorm_bwd(dolomite_stream_t stream,
                                     const void* dy, const void* s, const void* w,
                                     const float* rstd, void* dx, float* dw_partial,
                                     const void* dres, int64_t T_rows, int64_t H, int dtype) {
-    if (T_rows == 0) return 0;
-    hipStream_t stream_ = (hipStream_t)stream;
-    dim3 grid(RMS_BWD_BLOCKS), block(256);
-    if (dres == nullptr) {
-        if (dtype == DOLOMITE_BF16 && H % 8 == 0)
-            DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 8, 0,
-                              (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                              nullptr, rstd, (uint16_t*)dx, dw_partial, (const uint16_t*)dres, T_rows, (int)H);
-        else if (dtype == DOLOMITE_BF16)
-            DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 1, 0,
-                              (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                              nullptr, rstd, (uint16_t*)dx, dw_partial, (const uint16_t*)dres, T_rows, (int)H);
-        else if (H % 4 == 0)
-            DOL_NORM_DISPATCH(norm_bwd_kernel, float, 4, 0,
-                              (const float*)dy, (const float*)s, (const float*)w,
-                              nullptr, rstd, (float*)dx, dw_partial, (const float*)dres, T_rows, (int)H);
-        else
-            DOL_NORM_DISPATCH(norm_bwd_kernel, float, 1, 0,
-                              (const float*)dy, (const float*)s, (const float*)w,
-                              nullptr, rstd, (float*)dx, dw_partial, (const float*)dres, T_rows, (int)H);
-        return dol_last_error();
-    }
-    if (dtype == DOLOMITE_BF16 && H % 8 == 0)
-        DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 8, 2,
-                          (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                          nullptr, rstd, (uint16_t*)dx, dw_partial, (const uint16_t*)dres, T_rows, (int)H);
-    else if (dtype == DOLOMITE_BF16)
-        DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 1, 2,
-                          (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                          nullptr, rstd, (uint16_t*)dx, dw_partial, (const uint16_t*)dres, T_rows, (int)H);
-    else if (H % 4 == 0)
-        DOL_NORM_DISPATCH(norm_bwd_kernel, float, 4, 2,
-                          (const float*)dy, (const float*)s, (const float*)w,
-                          nullptr, rstd, (float*)dx, dw_partial, (const float*)dres, T_rows, (int)H);
-    else
-        DOL_NORM_DISPATCH(norm_bwd_kernel, float, 1, 2,
-                          (const float*)dy, (const float*)s, (const float*)w,
-                          nullptr, rstd, (float*)dx, dw_partial, (const float*)dres, T_rows, (int)H);
-    return dol_last_error();
+    return launch_norm_bwd<false>(stream, dy, s, w, nullptr, rstd, dx, dw_partial, dres, T_rows, H, dtype);
 }
 
 // ---------------------------------------------------------------------------
@@ -396,47 +376,16 @@ extern "C" int dolomite_layernorm_fwd(dolomite_stream_t stream,
                                       void* y, void* res_out, float* mean, float* rstd,
                                       int64_t T_rows, int64_t H, float eps, int dtype) {
     if (T_rows == 0) return 0;
-    hipStream_t stream_ = (hipStream_t)stream;
     dim3 grid((uint32_t)((T_rows + 3) / 4)), block(256);
-    bool has_res = res_in != nullptr;
-    if (dtype == DOLOMITE_BF16 && H % 8 == 0) {
-        if (has_res)
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, uint16_t, 8, true,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w, (const uint16_t*)b,
-                              (uint16_t*)y, (uint16_t*)res_out, mean, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, uint16_t, 8, false,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w, (const uint16_t*)b,
-                              (uint16_t*)y, (uint16_t*)res_out, mean, rstd, T_rows, (int)H, eps);
-    } else if (dtype == DOLOMITE_BF16) {
-        if (has_res)
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, uint16_t, 1, true,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w, (const uint16_t*)b,
-                              (uint16_t*)y, (uint16_t*)res_out, mean, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, uint16_t, 1, false,
-                              (const uint16_t*)x, (const uint16_t*)res_in, (const uint16_t*)w, (const uint16_t*)b,
-                              (uint16_t*)y, (uint16_t*)res_out, mean, rstd, T_rows, (int)H, eps);
-    } else if (H % 4 == 0) {
-        if (has_res)
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, float, 4, true,
-                              (const float*)x, (const float*)res_in, (const float*)w, (const float*)b,
-                              (float*)y, (float*)res_out, mean, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, float, 4, false,
-                              (const float*)x, (const float*)res_in, (const float*)w, (const float*)b,
-                              (float*)y, (float*)res_out, mean, rstd, T_rows, (int)H, eps);
-    } else {
-        if (has_res)
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, float, 1, true,
-                              (const float*)x, (const float*)res_in, (const float*)w, (const float*)b,
-                              (float*)y, (float*)res_out, mean, rstd, T_rows, (int)H, eps);
-        else
-            DOL_NORM_DISPATCH(layernorm_fwd_kernel, float, 1, false,
-                              (const float*)x, (const float*)res_in, (const float*)w, (const float*)b,
-                              (float*)y, (float*)res_out, mean, rstd, T_rows, (int)H, eps);
-    }
-    return dol_last_error();
+    return select_norm(dtype, H, [&](auto t, auto v, auto it) {
+        return select_bool(res_in != nullptr, [&](auto has_res) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((layernorm_fwd_kernel<T, v, it, has_res>), grid, block, 0, (hipStream_t)stream,
+                               (const T*)x, (const T*)res_in, (const T*)w, (const T*)b, (T*)y, (T*)res_out,
+                               mean, rstd, T_rows, (int)H, eps);
+            return dol_last_error();
+        });
+    });
 }
 
 extern "C" int dolomite_layernorm_bwd(dolomite_stream_t stream,
@@ -444,45 +393,7 @@ extern "C" int dolomite_layernorm_bwd(dolomite_stream_t stream,
                                       const float* mean, const float* rstd,
                                       void* dx, float* dwdb_partial,
                                       const void* dres, int64_t T_rows, int64_t H, int dtype) {
-    if (T_rows == 0) return 0;
-    hipStream_t stream_ = (hipStream_t)stream;
-    dim3 grid(RMS_BWD_BLOCKS), block(256);
-    if (dres == nullptr) {
-        if (dtype == DOLOMITE_BF16 && H % 8 == 0)
-            DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 8, 1,
-                              (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                              mean, rstd, (uint16_t*)dx, dwdb_partial, (const uint16_t*)dres, T_rows, (int)H);
-        else if (dtype == DOLOMITE_BF16)
-            DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 1, 1,
-                              (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                              mean, rstd, (uint16_t*)dx, dwdb_partial, (const uint16_t*)dres, T_rows, (int)H);
-        else if (H % 4 == 0)
-            DOL_NORM_DISPATCH(norm_bwd_kernel, float, 4, 1,
-                              (const float*)dy, (const float*)s, (const float*)w,
-                              mean, rstd, (float*)dx, dwdb_partial, (const float*)dres, T_rows, (int)H);
-        else
-            DOL_NORM_DISPATCH(norm_bwd_kernel, float, 1, 1,
-                              (const float*)dy, (const float*)s, (const float*)w,
-                              mean, rstd, (float*)dx, dwdb_partial, (const float*)dres, T_rows, (int)H);
-        return dol_last_error();
-    }
-    if (dtype == DOLOMITE_BF16 && H % 8 == 0)
-        DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 8, 3,
-                          (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                          mean, rstd, (uint16_t*)dx, dwdb_partial, (const uint16_t*)dres, T_rows, (int)H);
-    else if (dtype == DOLOMITE_BF16)
-        DOL_NORM_DISPATCH(norm_bwd_kernel, uint16_t, 1, 3,
-                          (const uint16_t*)dy, (const uint16_t*)s, (const uint16_t*)w,
-                          mean, rstd, (uint16_t*)dx, dwdb_partial, (const uint16_t*)dres, T_rows, (int)H);
-    else if (H % 4 == 0)
-        DOL_NORM_DISPATCH(norm_bwd_kernel, float, 4, 3,
-                          (const float*)dy, (const float*)s, (const float*)w,
-                          mean, rstd, (float*)dx, dwdb_partial, (const float*)dres, T_rows, (int)H);
-    else
-        DOL_NORM_DISPATCH(norm_bwd_kernel, float, 1, 3,
-                          (const float*)dy, (const float*)s, (const float*)w,
-                          mean, rstd, (float*)dx, dwdb_partial, (const float*)dres, T_rows, (int)H);
-    return dol_last_error();
+    return launch_norm_bwd<true>(stream, dy, s, w, mean, rstd, dx, dwdb_partial, dres, T_rows, H, dtype);
 }
 
 // ===========================================================================
@@ -656,32 +567,23 @@ extern "C" int dolomite_rope_qkv(dolomite_stream_t stream,
     (void)rotate_v_copy;
     if (D % 2 != 0) return 9003;
     float fdir = (dir >= 0) ? 1.f : -1.f;
-    if ((D / 2) % 8 == 0) {
-        int64_t total8 = T_rows * (int64_t)(H + Hkv) * (D / 2 / 8);
-        if (total8 == 0) return 0;
-        dim3 grid((uint32_t)((total8 + 255) / 256)), block(256);
-        if (dtype == DOLOMITE_BF16)
-            hipLaunchKernelGGL((rope_qkv_vec8_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream,
-                               (const uint16_t*)qkv_in, (uint16_t*)qkv_out, cos_t, sin_t,
-                               total8, row_len, H, Hkv, D, G, q_gstride, k_off, kv_hstride, fdir);
-        else
-            hipLaunchKernelGGL((rope_qkv_vec8_kernel<float>), grid, block, 0, (hipStream_t)stream,
-                               (const float*)qkv_in, (float*)qkv_out, cos_t, sin_t,
-                               total8, row_len, H, Hkv, D, G, q_gstride, k_off, kv_hstride, fdir);
-        return dol_last_error();
-    }
-    int64_t total = T_rows * (int64_t)(H + Hkv) * (D / 2);
+    bool vec8 = (D / 2) % 8 == 0;
+    // threads: one per 8 pairs (vec8) or one per pair
+    int64_t total = T_rows * (int64_t)(H + Hkv) * (vec8 ? D / 2 / 8 : D / 2);
     if (total == 0) return 0;
     dim3 grid((uint32_t)((total + 255) / 256)), block(256);
-    if (dtype == DOLOMITE_BF16)
-        hipLaunchKernelGGL((rope_qkv_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream,
-                           (const uint16_t*)qkv_in, (uint16_t*)qkv_out, cos_t, sin_t,
-                           total, row_len, H, Hkv, D, G, q_gstride, k_off, kv_hstride, fdir);
-    else
-        hipLaunchKernelGGL((rope_qkv_kernel<float>), grid, block, 0, (hipStream_t)stream,
-                           (const float*)qkv_in, (float*)qkv_out, cos_t, sin_t,
-                           total, row_len, H, Hkv, D, G, q_gstride, k_off, kv_hstride, fdir);
-    return dol_last_error();
+    return select_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (vec8)
+            hipLaunchKernelGGL((rope_qkv_vec8_kernel<T>), grid, block, 0, (hipStream_t)stream,
+                               (const T*)qkv_in, (T*)qkv_out, cos_t, sin_t,
+                               total, row_len, H, Hkv, D, G, q_gstride, k_off, kv_hstride, fdir);
+        else
+            hipLaunchKernelGGL((rope_qkv_kernel<T>), grid, block, 0, (hipStream_t)stream,
+                               (const T*)qkv_in, (T*)qkv_out, cos_t, sin_t,
+                               total, row_len, H, Hkv, D, G, q_gstride, k_off, kv_hstride, fdir);
+        return dol_last_error();
+    });
 }
 
 // ===========================================================================
@@ -747,22 +649,12 @@ extern "C" int dolomite_ce_fwd(dolomite_stream_t stream,
                                int64_t T_rows, int64_t V_dim, int64_t row_stride,
                                int ignore_index, int dtype) {
     dim3 grid((uint32_t)T_rows), block(256);
-    if (dtype == DOLOMITE_BF16) {
-        if (V_dim % 8 == 0)
-            hipLaunchKernelGGL((ce_fwd_kernel<uint16_t, 8>), grid, block, 0, (hipStream_t)stream,
-                               (const uint16_t*)logits, labels, row_loss, lse, V_dim, row_stride, ignore_index);
-        else
-            hipLaunchKernelGGL((ce_fwd_kernel<uint16_t, 1>), grid, block, 0, (hipStream_t)stream,
-                               (const uint16_t*)logits, labels, row_loss, lse, V_dim, row_stride, ignore_index);
-    } else {
-        if (V_dim % 4 == 0)
-            hipLaunchKernelGGL((ce_fwd_kernel<float, 4>), grid, block, 0, (hipStream_t)stream,
-                               (const float*)logits, labels, row_loss, lse, V_dim, row_stride, ignore_index);
-        else
-            hipLaunchKernelGGL((ce_fwd_kernel<float, 1>), grid, block, 0, (hipStream_t)stream,
-                               (const float*)logits, labels, row_loss, lse, V_dim, row_stride, ignore_index);
-    }
-    return dol_last_error();
+    return select_dtype_vec(dtype, V_dim, [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ce_fwd_kernel<T, v>), grid, block, 0, (hipStream_t)stream,
+                           (const T*)logits, labels, row_loss, lse, V_dim, row_stride, ignore_index);
+        return dol_last_error();
+    });
 }
 
 template <typename T, int V>
@@ -819,22 +711,13 @@ extern "C" int dolomite_ce_bwd(dolomite_stream_t stream,
                                int64_t T_rows, int64_t V_dim, int64_t row_stride,
                                int ignore_index, int dtype) {
     dim3 grid((uint32_t)T_rows), block(256);
-    if (dtype == DOLOMITE_BF16) {
-        if (V_dim % 8 == 0)
-            hipLaunchKernelGGL((ce_bwd_kernel<uint16_t, 8>), grid, block, 0, (hipStream_t)stream,
-                               (const uint16_t*)logits, labels, lse, (uint16_t*)dlogits, grad_scale_dev, V_dim, row_stride, ignore_index);
-        else
-            hipLaunchKernelGGL((ce_bwd_kernel<uint16_t, 1>), grid, block, 0, (hipStream_t)stream,
-                               (const uint16_t*)logits, labels, lse, (uint16_t*)dlogits, grad_scale_dev, V_dim, row_stride, ignore_index);
-    } else {
-        if (V_dim % 4 == 0)
-            hipLaunchKernelGGL((ce_bwd_kernel<float, 4>), grid, block, 0, (hipStream_t)stream,
-                               (const float*)logits, labels, lse, (float*)dlogits, grad_scale_dev, V_dim, row_stride, ignore_index);
-        else
-            hipLaunchKernelGGL((ce_bwd_kernel<float, 1>), grid, block, 0, (hipStream_t)stream,
-                               (const float*)logits, labels, lse, (float*)dlogits, grad_scale_dev, V_dim, row_stride, ignore_index);
-    }
-    return dol_last_error();
+    return select_dtype_vec(dtype, V_dim, [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ce_bwd_kernel<T, v>), grid, block, 0, (hipStream_t)stream,
+                           (const T*)logits, labels, lse, (T*)dlogits, grad_scale_dev,
+                           V_dim, row_stride, ignore_index);
+        return dol_last_error();
+    });
 }
 
 // ===========================================================================
@@ -919,13 +802,12 @@ extern "C" int dolomite_adamw_step(dolomite_stream_t stream,
     float bc2 = 1.f - powf(beta2, (float)step);
     int64_t nthreads = (n + 3) / 4;
     dim3 grid((uint32_t)((nthreads + 255) / 256)), block(256);
-    if (grad_dtype == DOLOMITE_BF16)
-        hipLaunchKernelGGL((adamw_kernel<1>), grid, block, 0, (hipStream_t)stream,
-                           master, (uint16_t*)param_out_bf16, grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, gscale);
-    else
-        hipLaunchKernelGGL((adamw_kernel<0>), grid, block, 0, (hipStream_t)stream,
-                           master, (uint16_t*)param_out_bf16, grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, gscale);
-    return dol_last_error();
+    return select_bool(grad_dtype == DOLOMITE_BF16, [&](auto grad_bf16) {
+        hipLaunchKernelGGL((adamw_kernel<grad_bf16>), grid, block, 0, (hipStream_t)stream,
+                           master, (uint16_t*)param_out_bf16, grad, m, v, n, lr, beta1, beta2, eps,
+                           weight_decay, bc1, bc2, gscale);
+        return dol_last_error();
+    });
 }
 
 // ===========================================================================
@@ -995,16 +877,15 @@ __global__ void __launch_bounds__(256) sqsum_fold_kernel(const float* __restrict
 extern "C" int dolomite_sqsum(dolomite_stream_t stream, const void* x, int64_t n,
                               float* partials, float* out, int dtype) {
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid(SQSUM_BLOCKS), block(256);
     if (n == 0) {
         (void)hipMemsetAsync(out, 0, sizeof(float), s);
         return dol_last_error();
     }
-    if (dtype == DOLOMITE_BF16)
-        hipLaunchKernelGGL((sqsum_kernel<uint16_t>), grid, block, 0, s, (const uint16_t*)x, n, partials);
-    else
-        hipLaunchKernelGGL((sqsum_kernel<float>), grid, block, 0, s, (const float*)x, n, partials);
-    int err = dol_last_error();
+    int err = select_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((sqsum_kernel<T>), dim3(SQSUM_BLOCKS), dim3(256), 0, s, (const T*)x, n, partials);
+        return dol_last_error();
+    });
     if (err) return err;
     // one block, fixed tree (1024 scalars: not worth reduce_partials' two passes)
     hipLaunchKernelGGL((sqsum_fold_kernel), dim3(1), dim3(256), 0, s, partials, out);
@@ -1030,11 +911,11 @@ extern "C" int dolomite_scale_inplace(dolomite_stream_t stream, void* buf, int64
     if (n == 0) return 0;
     int64_t nthreads = (n + 3) / 4;
     dim3 grid((uint32_t)((nthreads + 255) / 256)), block(256);
-    if (dtype == DOLOMITE_BF16)
-        hipLaunchKernelGGL((scale_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream, (uint16_t*)buf, n, scale);
-    else
-        hipLaunchKernelGGL((scale_kernel<float>), grid, block, 0, (hipStream_t)stream, (float*)buf, n, scale);
-    return dol_last_error();
+    return select_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((scale_kernel<T>), grid, block, 0, (hipStream_t)stream, (T*)buf, n, scale);
+        return dol_last_error();
+    });
 }
 
 extern "C" int dolomite_hip_abi_version(void) { return 2; }

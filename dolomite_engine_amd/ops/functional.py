@@ -108,29 +108,71 @@ def _rmsnorm_bwd_cpu(dy, s, w, rstd, dtype):
     return dx, dw
 
 
+def _norm_fwd_gpu(name, x2, residual, params, eps):
+    """GPU forward of both fused norms. name: "rmsnorm" with params (weight,),
+    or "layernorm" with params (weight, bias). Returns y, s and the fp32 row
+    statistics the backward needs: [rstd], or [mean, rstd]."""
+    rows, H = x2.shape
+    x2 = x2.contiguous()
+    res2 = residual.reshape(-1, H).contiguous() if residual is not None else None
+    y = torch.empty_like(x2)
+    # without a residual the pre-norm sum is x2 itself and res_out is null
+    s = torch.empty_like(x2) if residual is not None else x2
+    # rstd | mean, rstd: each norm keeps as many row statistics as it has parameters
+    stats = [torch.empty(rows, dtype=torch.float32, device=x2.device) for _ in params]
+    with hip.prof(f"{name}_fwd"):
+        hip.check(
+            getattr(hip.lib(), f"dolomite_{name}_fwd")(
+                hip.stream(), hip.ptr(x2), hip.ptr(res2), *map(hip.ptr, params),
+                hip.ptr(y), hip.ptr(s if residual is not None else None),
+                *map(hip.ptr, stats), rows, H, float(eps), hip.dt(x2),
+            ),
+            f"{name}_fwd",
+        )
+    return y, s, stats
+
+
+def _norm_bwd_gpu(name, dy2, ds, s, weight, stats):
+    """GPU backward of both fused norms (stats as _norm_fwd_gpu returned them).
+    Returns dx and the parameter grads in weight.dtype: [dw], or [dw, db]."""
+    rows, H = s.shape
+    dy2 = dy2.contiguous()
+    ds2 = ds.reshape(-1, H).contiguous() if ds is not None else None
+    dx = torch.empty_like(s)
+    nb = hip.lib().dolomite_rmsnorm_bwd_nblocks(rows)
+    # one block of nb partial rows per parameter grad: dw's, then layernorm's db's
+    partial = torch.empty(len(stats) * nb, H, dtype=torch.float32, device=s.device)
+    with hip.prof(f"{name}_bwd"):
+        hip.check(
+            getattr(hip.lib(), f"dolomite_{name}_bwd")(
+                hip.stream(), hip.ptr(dy2), hip.ptr(s), hip.ptr(weight), *map(hip.ptr, stats),
+                hip.ptr(dx), hip.ptr(partial),
+                hip.ptr(ds2),  # residual-stream grad folded into dx in-kernel
+                rows, H, hip.dt(s),
+            ),
+            f"{name}_bwd",
+        )
+    # fixed-order reduce (reduce_partials_ref): the grads are bitwise reproducible
+    grads = [torch.empty(H, dtype=torch.float32, device=s.device) for _ in stats]
+    with hip.prof("reduce_partials"):
+        for i, g in enumerate(grads):
+            hip.check(
+                hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(partial, i * nb * H), hip.ptr(g), nb, H),
+                "reduce_partials",
+            )
+    return dx, [g.to(weight.dtype) for g in grads]
+
+
 class FusedRMSNorm(torch.autograd.Function):
     """y, s = rmsnorm(x [+ residual]); s is the pre-norm sum (next residual).
     Semantics: rmsnorm/base.py:18-25 (fp32 accum, cast before weight)."""
 
     @staticmethod
     def forward(ctx, x, weight, eps, residual):
-        T, H = x.shape[0], x.shape[-1]
+        H = x.shape[-1]
         x2 = x.reshape(-1, H)
         if x2.is_cuda:
-            x2 = x2.contiguous()
-            res2 = residual.reshape(-1, H).contiguous() if residual is not None else None
-            y = torch.empty_like(x2)
-            s = torch.empty_like(x2) if residual is not None else x2
-            rstd = torch.empty(x2.shape[0], dtype=torch.float32, device=x2.device)
-            with hip.prof("rmsnorm_fwd"):
-             hip.check(
-                hip.lib().dolomite_rmsnorm_fwd(
-                    hip.stream(), hip.ptr(x2), hip.ptr(res2), hip.ptr(weight),
-                    hip.ptr(y), hip.ptr(s) if residual is not None else hip.ptr(None),
-                    hip.ptr(rstd), x2.shape[0], H, float(eps), hip.dt(x2),
-                ),
-                "rmsnorm_fwd",
-            )
+            y, s, (rstd,) = _norm_fwd_gpu("rmsnorm", x2, residual, (weight,), eps)
         else:
             y, s, rstd = _rmsnorm_fwd_cpu(x2, residual.reshape(-1, H) if residual is not None else None, weight, eps)
         ctx.save_for_backward(s, weight, rstd)
@@ -144,29 +186,7 @@ class FusedRMSNorm(torch.autograd.Function):
         H = s.shape[-1]
         dy2 = dy.reshape(-1, H)
         if s.is_cuda:
-            dy2 = dy2.contiguous()
-            ds2 = ds.reshape(-1, H).contiguous() if ds is not None else None
-            dx = torch.empty_like(s)
-            nb = hip.lib().dolomite_rmsnorm_bwd_nblocks(s.shape[0])
-            dw_partial = torch.empty(nb, H, dtype=torch.float32, device=s.device)
-            with hip.prof("rmsnorm_bwd"):
-             hip.check(
-                hip.lib().dolomite_rmsnorm_bwd(
-                    hip.stream(), hip.ptr(dy2), hip.ptr(s), hip.ptr(weight),
-                    hip.ptr(rstd), hip.ptr(dx), hip.ptr(dw_partial),
-                    hip.ptr(ds2),  # residual-stream grad folded into dx in-kernel
-                    s.shape[0], H, hip.dt(s),
-                ),
-                "rmsnorm_bwd",
-            )
-            # fixed-order reduce (reduce_partials_ref): dw is bitwise reproducible
-            dw32 = torch.empty(H, dtype=torch.float32, device=s.device)
-            with hip.prof("reduce_partials"):
-                hip.check(
-                    hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dw_partial), hip.ptr(dw32), nb, H),
-                    "reduce_partials",
-                )
-            dw = dw32.to(weight.dtype)
+            dx, (dw,) = _norm_bwd_gpu("rmsnorm", dy2, ds, s, weight, (rstd,))
             dx = dx.view(ctx.shape)
         else:
             dx, dw = _rmsnorm_bwd_cpu(dy2, s, weight, rstd, dy.dtype)
@@ -223,20 +243,7 @@ class FusedLayerNorm(torch.autograd.Function):
         H = x.shape[-1]
         x2 = x.reshape(-1, H)
         if x2.is_cuda:
-            x2 = x2.contiguous()
-            res2 = residual.reshape(-1, H).contiguous() if residual is not None else None
-            y = torch.empty_like(x2)
-            s = torch.empty_like(x2) if residual is not None else x2
-            mean = torch.empty(x2.shape[0], dtype=torch.float32, device=x2.device)
-            rstd = torch.empty_like(mean)
-            hip.check(
-                hip.lib().dolomite_layernorm_fwd(
-                    hip.stream(), hip.ptr(x2), hip.ptr(res2), hip.ptr(weight), hip.ptr(bias),
-                    hip.ptr(y), hip.ptr(s) if residual is not None else hip.ptr(None),
-                    hip.ptr(mean), hip.ptr(rstd), x2.shape[0], H, float(eps), hip.dt(x2),
-                ),
-                "layernorm_fwd",
-            )
+            y, s, (mean, rstd) = _norm_fwd_gpu("layernorm", x2, residual, (weight, bias), eps)
         else:
             y, s, mean, rstd = _layernorm_fwd_cpu(
                 x2, residual.reshape(-1, H) if residual is not None else None, weight, bias, eps
@@ -252,30 +259,7 @@ class FusedLayerNorm(torch.autograd.Function):
         H = s.shape[-1]
         dy2 = dy.reshape(-1, H)
         if s.is_cuda:
-            dy2 = dy2.contiguous()
-            ds2 = ds.reshape(-1, H).contiguous() if ds is not None else None
-            dx = torch.empty_like(s)
-            nb = hip.lib().dolomite_rmsnorm_bwd_nblocks(s.shape[0])
-            dwdb = torch.empty(2 * nb, H, dtype=torch.float32, device=s.device)
-            hip.check(
-                hip.lib().dolomite_layernorm_bwd(
-                    hip.stream(), hip.ptr(dy2), hip.ptr(s), hip.ptr(weight),
-                    hip.ptr(mean), hip.ptr(rstd), hip.ptr(dx), hip.ptr(dwdb),
-                    hip.ptr(ds2), s.shape[0], H, hip.dt(s),
-                ),
-                "layernorm_bwd",
-            )
-            # dw partials are rows [0, nb), db rows [nb, 2nb) — reduce both
-            # halves separately, each in the fixed order of reduce_partials_ref
-            dw32 = torch.empty(H, dtype=torch.float32, device=s.device)
-            db32 = torch.empty(H, dtype=torch.float32, device=s.device)
-            with hip.prof("reduce_partials"):
-                hip.check(hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dwdb), hip.ptr(dw32), nb, H), "rp")
-                hip.check(
-                    hip.lib().dolomite_reduce_partials(hip.stream(), hip.ptr(dwdb, nb * H), hip.ptr(db32), nb, H), "rp"
-                )
-            dw = dw32.to(weight.dtype)
-            db = db32.to(weight.dtype)
+            dx, (dw, db) = _norm_bwd_gpu("layernorm", dy2, ds, s, weight, (mean, rstd))
             dx = dx.view(ctx.shape)
         else:
             s32 = s.float()
