@@ -52,13 +52,11 @@
 //   B[k][j]: lane l holds k = (l>>4)*8 + e, j = l&15
 //   C[r][c]: lane l, reg x holds r = (l>>4)*4 + x, c = l&15
 
-#include "common.h"
+// The parts all three hot kernels share — fragment types, the tr16 ladder,
+// the guarded load, row reductions, the transposed epilogue store, the K/V
+// image geometry — live in mfma_tiles.h (decode.hip uses some of them too).
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+#include "mfma_tiles.h"
 
 // softmax runs in the exp2 domain: v_exp_f32 natively computes 2^x, so
 // folding log2(e) into the softmax scale removes one multiply per element
@@ -89,8 +87,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------
 #define PI23(q) (((q) & ~12) | ((((q) >> 2) & 1) << 3) | ((((q) >> 3) & 1) << 2))
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 // The reads and their waitcnt MUST live in one asm block: the compiler
 // assumes an asm statement completes synchronously, so with a separate wait
 // it is free to copy/shuffle the "ready" result registers before the data
@@ -118,76 +114,6 @@ __device__ __forceinline__ bf16x8 lds_tr16_bfrag(const __bf16* img, int rowbase,
 #pragma unroll
     for (int t = 0; t < 4; ++t) { out[t] = lo[t]; out[4 + t] = hi[t]; }
     return out;
-}
-
-// ---------------------------------------------------------------------------
-// Pipelined tr16 ladder (guide §5.7 forms (i)/(ii) + T3/T4 counted waits).
-//
-// Round 1 measured that per-fragment `lgkmcnt(0)` drains serialize the MFMA
-// stream (each tr16 read's 50-cycle latency lands on the critical path).
-// The ladder splits issue and wait: fragment i+1's reads are issued BEFORE
-// waiting on fragment i with a counted `lgkmcnt(N)` (N = the just-issued
-// reads), so LDS latency hides under the current fragment's MFMAs and the
-// counter never drains to 0 inside the loop.
-//
-// Count discipline: the ladder's waits are exact only if no OTHER lgkm op
-// is outstanding, so each region (a) opens with nothing in flight — every
-// earlier LDS read has already been consumed by a score MFMA or the
-// softmax — and (b) is fenced with sched_barrier(0)
-// so the compiler cannot move its own ds/smem ops inside.
-// ---------------------------------------------------------------------------
-
-// Issue one B-fragment's two transpose reads (no wait): OFF = byte offset of
-// the (rowbase, d0) chunk inside the image, a0/a1 = the lane's two row base
-// addresses (computed once per kernel).
-template <int OFF>
-__device__ __forceinline__ void tr16_issue(unsigned a0, unsigned a1, bf16x4& lo, bf16x4& hi) {
-    asm volatile(
-        "ds_read_b64_tr_b16 %0, %2 offset:%c4\n\t"
-        "ds_read_b64_tr_b16 %1, %3 offset:%c4"
-        : "=&v"(lo), "=&v"(hi)
-        : "v"(a0), "v"(a1), "i"(OFF)
-        : "memory");
-}
-
-// Counted wait naming the registers it guarantees (guide §5.7 form (ii)).
-template <int N>
-__device__ __forceinline__ void lgkm_wait2(bf16x4& a, bf16x4& b) {
-    asm volatile("s_waitcnt lgkmcnt(%c2)" : "+v"(a), "+v"(b) : "i"(N));
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait4(bf16x4& a, bf16x4& b, bf16x4& c, bf16x4& d) {
-    asm volatile("s_waitcnt lgkmcnt(%c4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "i"(N));
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait8(bf16x4& a, bf16x4& b, bf16x4& c, bf16x4& d,
-                                           bf16x4& e, bf16x4& f, bf16x4& g, bf16x4& h) {
-    asm volatile("s_waitcnt lgkmcnt(%c8)"
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h)
-                 : "i"(N));
-}
-
-__device__ __forceinline__ bf16x8 tr16_join8(bf16x4 lo, bf16x4 hi) {
-    bf16x8 out;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { out[t] = lo[t]; out[4 + t] = hi[t]; }
-    return out;
-}
-
-// Branchless guarded 16B load. Requires D % 8 == 0 (every head dim on this
-// path): a chunk is then fully inside [0, D) or fully in the pad, so the
-// guard reduces to ONE wave-divergent-free vector load from a clamped
-// address plus per-element selects. (The original branchy version emitted
-// 8 scalar loads + a vector load per fragment and forced hipcc to drain
-// vmcnt(0) before every dependent MFMA — the dominant stall of round 1's
-// backward kernel.)
-__device__ __forceinline__ bf16x8 load_bf16x8_guard(const __bf16* p, int d0, int D, bool valid) {
-    const __bf16* q = (d0 < D) ? p : (p - d0);  // clamp into the row
-    bool ok = valid && (d0 < D);
-    bf16x8 r = *(const bf16x8*)q;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = ok ? r[e] : (__bf16)0.f;
-    return r;
 }
 
 // XCD-aware block remap (guide T1): the dispatcher places flat block id b on
@@ -288,46 +214,6 @@ static inline bool drop_p_valid(float p_drop) { return p_drop >= 0.f && p_drop <
 // q on l & 15): 4 contiguous bf16 per lane and block, one 8-byte store.
 // ===========================================================================
 
-// K/V image geometry shared by the fwd and dq kernels and their launchers:
-// two 64-row images of stride S and, with dropout, the staged tile's 64
-// keep-mask column words behind them — nothing else in dynamic LDS.
-template <int DPAD>
-struct FaKvLds {
-    static constexpr int S = DPAD + 16;
-    static constexpr size_t image_bytes = (size_t)2 * 64 * S * sizeof(__bf16);  // multiple of 256
-    static constexpr size_t bytes(bool dropout) {
-        return image_bytes + (dropout ? 64 * sizeof(uint32_t) : 0);
-    }
-};
-
-// lane base addresses (reads h = 0, 1) of the permuted-key tr16 ladder over
-// a natural-row image of stride S
-__device__ __forceinline__ void fa_tr16_perm_bases(const __bf16* img, int S, int lane,
-                                                   unsigned& a0, unsigned& a1) {
-    const int row = (lane >> 4) * 4 + ((lane >> 2) & 3);
-    const int cc = (lane & 3) * 4;
-    a0 = (unsigned)(size_t)(img + row * S + cc);
-    a1 = (unsigned)(size_t)(img + (16 + row) * S + cc);
-}
-
-// Reductions over the 4 lanes {l, l^16, l^32, l^48} that share one q row:
-// v_permlane16_swap exchanges the odd 16-lane rows of its first operand with
-// the even rows of its second, v_permlane32_swap the upper half-wave of the
-// first with the lower half of the second. With both operands the same
-// value each returned pair holds (own, partner) on every lane. Pure VALU.
-__device__ __forceinline__ float qgroup_reduce_max(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float qgroup_reduce_sum(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
 // ===========================================================================
 // Forward
 // ===========================================================================
@@ -343,11 +229,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
     constexpr int KCH = DPAD / 32;   // contraction chunks for QK^T
     constexpr int DCH = DPAD / 16;   // output row blocks of O^T
-    // Stride chosen with tools_lds_sim.py (exact gfx950 bank model): DPAD+16
-    // makes the b128 row reads of the K image, the b128 staging writes and
-    // the key-permuted tr16 reads of the V image (8 consecutive rows per
-    // 32-lane pass) all conflict-free with rows in natural order.
-    constexpr int SK = FaKvLds<DPAD>::S;   // K/V LDS row stride (elems)
+    constexpr int SK = FaKvLds<DPAD>::S;   // K/V LDS row stride (elems), conflict-free (mfma_tiles.h)
 
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
@@ -379,8 +261,9 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     //       (T20) and issues some chunk DMAs under partial exec masks, so
     //       inactive lanes leave stale LDS in the image (flaky parity
     //       failures across runs; see git history for the full variant).
-    // At 2 workgroups/CU the co-resident workgroup already hides staging
-    // latency, so the single-buffer two-barrier schedule stays.
+    // The (512, 4) bound (<= 128 VGPR, 4 waves/SIMD) keeps 2 of these
+    // 8-wave workgroups on a CU: the co-resident workgroup already hides
+    // staging latency, so the single-buffer two-barrier schedule stays.
     extern __shared__ char smem_raw[];             // FaKvLds<DPAD>::bytes(DROPOUT)
     __bf16* Klds = (__bf16*)smem_raw;              // [64 key][SK]
     __bf16* Vlds = Klds + 64 * SK;                 // [64 key][SK]
@@ -487,6 +370,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
         }
     };
 
+
     // softmax scale folded into the exponent as one FMA per score; the row
     // max is taken on the raw scores, which orders them alike for scale > 0
     // (the dispatcher rejects anything else)
@@ -564,35 +448,15 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
         // counted-wait frag i, MFMA — LDS latency hides under the matrix
         // pipe). The K reads above were consumed by the score MFMAs, so no
         // LDS op is outstanding when the ladder opens. ---
-        {
-            __builtin_amdgcn_sched_barrier(0);
-            // depth-3 pipeline: two fragments stay in flight — ONE MFMA
-            // (~17 cyc) does not cover the ~50-cycle LDS read latency that
-            // depth-2 exposed at every counted wait
-            bf16x4 vlo[3], vhi[3];
-            tr16_issue<0>(aV0c, aV1c, vlo[0], vhi[0]);
-            tr16_issue<((1 / DCH) * 32 * SK + (1 % DCH) * 16) * 2>(aV0c, aV1c, vlo[1], vhi[1]);
-#define FWD_PV_STEP(i)                                                                                  \
-    if constexpr ((i) < 2 * DCH) {                                                                      \
-        constexpr int kc2_ = (i) / DCH, dc_ = (i) % DCH;                                                \
-        if constexpr ((i) + 2 < 2 * DCH) {                                                              \
-            constexpr int kn_ = ((i) + 2) / DCH, dn_ = ((i) + 2) % DCH;                                 \
-            tr16_issue<(kn_ * 32 * SK + dn_ * 16) * 2>(aV0c, aV1c, vlo[((i) + 2) % 3], vhi[((i) + 2) % 3]); \
-            lgkm_wait2<4>(vlo[(i) % 3], vhi[(i) % 3]);                                                  \
-        } else if constexpr ((i) + 1 < 2 * DCH) {                                                       \
-            lgkm_wait2<2>(vlo[(i) % 3], vhi[(i) % 3]);                                                  \
-        } else {                                                                                        \
-            lgkm_wait2<0>(vlo[(i) % 3], vhi[(i) % 3]);                                                  \
-        }                                                                                               \
-        o_acc[dc_] = MFMA16(tr16_join8(vlo[(i) % 3], vhi[(i) % 3]), pf[kc2_], o_acc[dc_]);              \
-    }
-            FWD_PV_STEP(0) FWD_PV_STEP(1) FWD_PV_STEP(2) FWD_PV_STEP(3)
-            FWD_PV_STEP(4) FWD_PV_STEP(5) FWD_PV_STEP(6) FWD_PV_STEP(7)
-            FWD_PV_STEP(8) FWD_PV_STEP(9) FWD_PV_STEP(10) FWD_PV_STEP(11)
-            FWD_PV_STEP(12) FWD_PV_STEP(13) FWD_PV_STEP(14) FWD_PV_STEP(15)
-#undef FWD_PV_STEP
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        // depth-3 pipeline: two fragments stay in flight — ONE MFMA
+        // (~17 cyc) does not cover the ~50-cycle LDS read latency that
+        // depth-2 exposed at every counted wait
+        tr16_ladder<3, 2 * DCH>(
+            aV0c, aV1c, [](int i) { return ((i / DCH) * 32 * SK + (i % DCH) * 16) * 2; },
+            [&](auto i, bf16x8 vf) {
+                constexpr int kc2 = decltype(i)::value / DCH, dc = decltype(i)::value % DCH;
+                o_acc[dc] = MFMA16(vf, pf[kc2], o_acc[dc]);
+            });
     };
 
     for (int kt = 0; kt < ntiles; ++kt) {
@@ -613,16 +477,8 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     if constexpr (DROPOUT) inv_l *= drop_rp;  // kept P scaled by 1/(1-p)
     if (lg == 0 && qvalid)
         lse[(int64_t)h * T_total + s0 + qrow] = (m_run + log2f(l_row)) * DOL_LN2;
-    // D % 8 == 0 on this path: a 4-wide group is all inside D or all pad
     __bf16* orow = o + (int64_t)(s0 + (qvalid ? qrow : 0)) * o_ts + (int64_t)h * D;
-#pragma unroll
-    for (int dc = 0; dc < DCH; ++dc) {
-        const int d0 = dc * 16 + lg * 4;
-        bf16x4 ov;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) ov[x] = (__bf16)(o_acc[dc][x] * inv_l);
-        if (qvalid && d0 < D) *(bf16x4*)&orow[d0] = ov;
-    }
+    fa_store_rowT_bf16<DCH>(orow, o_acc, inv_l, qvalid, D, lg);
 }
 
 // One causal-attention problem over the row spans [seq_begin[b], seq_end[b]),
@@ -988,10 +844,6 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
     const int64_t q_hoff = (int64_t)(h / G) * q_gs + (int64_t)(h % G) * D;
     const int64_t do_hoff = (int64_t)h * D;
 
-    // MFMA pad columns [D, DPAD) zeroed ONCE: the fast staging path below
-    // then only writes the real D columns per tile (guards and pad-fill
-    // gone from the per-tile loop; the guarded edge path rewrites pads
-    // with zeros, so the invariant holds under any tile interleave)
     if (D < DPAD) {
         for (int pidx = threadIdx.x; pidx < 64 * (DPAD - D) / 8; pidx += 512) {
             int qq = pidx / ((DPAD - D) / 8);
@@ -1068,35 +920,16 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
             }
         }
 
-        __builtin_amdgcn_sched_barrier(0);
-        constexpr int CB = c * 32 * SQ * 2;    // the chunk's 32 image rows (bytes)
-        bf16x4 alo[3], ahi[3];
-        tr16_issue<CB + DO_IMM>(aQ0, aQ1, alo[0], ahi[0]);
-        static_assert(DCH >= 2, "fragment 1 is the dO image's second 16-col block");
-        tr16_issue<CB + DO_IMM + 32>(aQ0, aQ1, alo[1], ahi[1]);
-#define DKV_STEP(i)                                                                                     \
-    if constexpr ((i) < 2 * DCH) {                                                                      \
-        constexpr int im_ = (i) / DCH, dc_ = (i) % DCH;                                                 \
-        if constexpr ((i) + 2 < 2 * DCH) {                                                              \
-            constexpr int in_ = ((i) + 2) / DCH, dn_ = ((i) + 2) % DCH;                                 \
-            tr16_issue<CB + (in_ ? 0 : DO_IMM) + dn_ * 32>(aQ0, aQ1, alo[((i) + 2) % 3], ahi[((i) + 2) % 3]); \
-            lgkm_wait2<4>(alo[(i) % 3], ahi[(i) % 3]);                                                  \
-        } else if constexpr ((i) + 1 < 2 * DCH) {                                                       \
-            lgkm_wait2<2>(alo[(i) % 3], ahi[(i) % 3]);                                                  \
-        } else {                                                                                        \
-            lgkm_wait2<0>(alo[(i) % 3], ahi[(i) % 3]);                                                  \
-        }                                                                                               \
-        if constexpr (im_ == 0)                                                                         \
-            dvr[dc_] = MFMA16(tr16_join8(alo[(i) % 3], ahi[(i) % 3]), pf, dvr[dc_]);                    \
-        else                                                                                            \
-            dkr[dc_] = MFMA16(tr16_join8(alo[(i) % 3], ahi[(i) % 3]), dsf, dkr[dc_]);                   \
-    }
-        DKV_STEP(0) DKV_STEP(1) DKV_STEP(2) DKV_STEP(3)
-        DKV_STEP(4) DKV_STEP(5) DKV_STEP(6) DKV_STEP(7)
-        DKV_STEP(8) DKV_STEP(9) DKV_STEP(10) DKV_STEP(11)
-        DKV_STEP(12) DKV_STEP(13) DKV_STEP(14) DKV_STEP(15)
-#undef DKV_STEP
-        __builtin_amdgcn_sched_barrier(0);
+        // fragments 0 .. DCH-1 walk the dO image (dV), DCH .. 2*DCH-1 the Q
+        // image (dK), both from the chunk's 32 image rows at c * 32 * SQ * 2 bytes
+        tr16_ladder<3, 2 * DCH>(
+            aQ0, aQ1,
+            [](int i) { return c * 32 * SQ * 2 + (i / DCH ? 0 : DO_IMM) + (i % DCH) * 32; },
+            [&](auto i, bf16x8 af) {
+                constexpr int dc = decltype(i)::value % DCH;
+                if constexpr (decltype(i)::value / DCH == 0) dvr[dc] = MFMA16(af, pf, dvr[dc]);
+                else dkr[dc] = MFMA16(af, dsf, dkr[dc]);
+            });
     };
 
     // (hoisting the staging coordinates like dq/fwd costs 3 scratch
@@ -1327,10 +1160,10 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
                     *(bf16x8*)&Vlds[key * SQ + d0] = load_bf16x8_guard(vp, d0, D, valid);
                 }
             }
-            if constexpr (DROPOUT) {
-                if (__builtin_amdgcn_readfirstlane(threadIdx.x) < 64)
-                    Cw[lane] = drop_col_word(drop_hw, (uint32_t)(s0 + ks + lane));
-            }
+        }
+        if constexpr (DROPOUT) {
+            if (__builtin_amdgcn_readfirstlane(threadIdx.x) < 64)
+                Cw[lane] = drop_col_word(drop_hw, (uint32_t)(s0 + ks + lane));
         }
         __syncthreads();
 
@@ -1382,7 +1215,11 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
 
         // dQ^T += K^T*dS^T (contraction over this tile's keys) — pipelined
         // tr16 ladder over the K image; the image reads above were consumed
-        // by the score MFMAs, so no LDS op is outstanding when it opens
+        // by the score MFMAs, so no LDS op is outstanding when it opens.
+        // Hand-expanded on the shared primitives, not tr16_ladder<4, N>: on
+        // the template the six DPAD >= 64 instantiations compiled to other
+        // prologues (dq<96, false> +2 VGPRs) and one missed the A/B
+        // (profiles/attn_shared_ab_bench.txt).
         {
             __builtin_amdgcn_sched_barrier(0);
             // depth-4 rotation: 3 fragments in flight per wait (the dq cap
@@ -1417,18 +1254,9 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     }
 
     // single bf16 store of the accumulated dQ^T straight into the packed
-    // dqkv (each (t, h, d) is owned by exactly one q-tile workgroup): 4
-    // contiguous head-dim elements per lane and block (D % 8 == 0, so a
-    // group is all inside D or all pad)
+    // dqkv (each (t, h, d) is owned by exactly one q-tile workgroup)
     __bf16* dqrow = dqkv_q + (int64_t)(s0 + (qvalid ? qrow : 0)) * q_ts + q_hoff;
-#pragma unroll
-    for (int dc = 0; dc < DCH; ++dc) {
-        const int d0 = dc * 16 + lg * 4;
-        bf16x4 dv;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) dv[x] = (__bf16)dq[dc][x];
-        if (qvalid && d0 < D) *(bf16x4*)&dqrow[d0] = dv;
-    }
+    fa_store_rowT_bf16<DCH>(dqrow, dq, 1.f, qvalid, D, lg);
 }
 
 template <int DPAD, bool DROPOUT>

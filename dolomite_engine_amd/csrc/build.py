@@ -22,7 +22,7 @@ def _needs_rebuild() -> bool:
     if not SO_PATH.exists():
         return True
     so_mtime = SO_PATH.stat().st_mtime
-    deps = SOURCES + [CSRC / "common.h", REPO / "include" / "dolomite_hip.h"]
+    deps = SOURCES + [CSRC / "common.h", CSRC / "mfma_tiles.h", REPO / "include" / "dolomite_hip.h"]
     return any(p.stat().st_mtime > so_mtime for p in deps)
 
 

@@ -5,8 +5,8 @@
 // cache, attention/flash.py query_length == 1 branch): ONE query token per
 // sequence attends over that sequence's cached keys. One query row per head
 // makes the step HBM-bound on the K/V read, the opposite regime of
-// attention.hip, so it has its own kernels here and shares no code object
-// with the training kernels (the few small device helpers are duplicated).
+// attention.hip, so it has its own kernels here; the fragment types, the
+// guarded load and the 4-lane reductions come from mfma_tiles.h.
 //
 // Design:
 //   - grid (nsplit, batch, Hkv * head groups): split c of sequence b owns
@@ -36,33 +36,18 @@
 // Fragment layouts: see attention.hip (verified by dolomite_mfma_probe and
 // dolomite_tr16_probe).
 
-#include "common.h"
+#include "mfma_tiles.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 #define DEC_LOG2E 1.44269504088896340736f
 
 #define DEC_WAVES 4      // waves per workgroup
 #define DEC_KTILE 64     // keys per wave step
 
-// Branchless guarded 16B load (attention.hip load_bf16x8_guard): with
-// D % 8 == 0 a chunk is fully inside [0, D) or fully in the pad. The caller
-// passes an in-bounds row; `valid` false or a pad chunk selects zero.
-__device__ __forceinline__ bf16x8 dec_load8_guard(const __bf16* p, int d0, int D, bool valid) {
-    const __bf16* q = (d0 < D) ? p : (p - d0);  // clamp into the row
-    bool ok = valid && (d0 < D);
-    bf16x8 r = *(const bf16x8*)q;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = ok ? r[e] : (__bf16)0.f;
-    return r;
-}
-
 // One V^T A-fragment: two transpose reads of the row-major image in the
 // permuted key order of attention.hip "Swapped-operand score tiles". The
-// reads and their wait live in one asm block (see attention.hip).
+// reads and their wait live in one asm block (see attention.hip): the step is
+// HBM-bound, so there is no lookahead and no use for the counted ladder of
+// mfma_tiles.h (moving the reads onto it changed every instantiation's code).
 template <int OFF>
 __device__ __forceinline__ bf16x8 dec_tr16_frag(unsigned a0, unsigned a1) {
     bf16x4 lo, hi;
@@ -77,20 +62,6 @@ __device__ __forceinline__ bf16x8 dec_tr16_frag(unsigned a0, unsigned a1) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) { out[t] = lo[t]; out[4 + t] = hi[t]; }
     return out;
-}
-
-// max over the 4 lanes {l, l^16, l^32, l^48} that share one head (pure VALU)
-__device__ __forceinline__ float dec_hgroup_max(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float dec_hgroup_sum(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 
 // Per-wave LDS region: the V image [64 key][DPAD+16] bf16 during the key
@@ -155,7 +126,7 @@ __global__ void __launch_bounds__(DEC_WAVES * 64, 2) fa_decode_kernel(
 #pragma unroll
         for (int c = 0; c < KCH; ++c) {
             const int d0 = c * 32 + lg * 8;
-            qf[hb][c] = dec_load8_guard(qrow + (int64_t)(hvalid ? g : 0) * D + d0, d0, D, hvalid);
+            qf[hb][c] = load_bf16x8_guard(qrow + (int64_t)(hvalid ? g : 0) * D + d0, d0, D, hvalid);
         }
     }
 
@@ -199,7 +170,7 @@ __global__ void __launch_bounds__(DEC_WAVES * 64, 2) fa_decode_kernel(
 #pragma unroll
             for (int c = 0; c < KCH; ++c) {
                 const int d0 = c * 32 + lg * 8;
-                kf[cb][c] = dec_load8_guard(kp + d0, d0, D, true);
+                kf[cb][c] = load_bf16x8_guard(kp + d0, d0, D, true);
             }
         }
         bf16x8 vp[VPIECES];
@@ -210,7 +181,7 @@ __global__ void __launch_bounds__(DEC_WAVES * 64, 2) fa_decode_kernel(
             const int d0 = (pidx % (DPAD / 8)) * 8;
             const bool kvalid = ks + key < kend;
             const __bf16* p = vbase + (int64_t)min(ks + key, kend - 1) * v_ts + d0;
-            vp[j] = dec_load8_guard(p, d0, D, kvalid);
+            vp[j] = load_bf16x8_guard(p, d0, D, kvalid);
         }
 
         // --- S^T = K*Q^T: sc[hb][cb][x] is (head g0+16hb+lr,
@@ -249,7 +220,7 @@ __global__ void __launch_bounds__(DEC_WAVES * 64, 2) fa_decode_kernel(
                     sc[hb][cb][x] = (kpos < kend) ? sc[hb][cb][x] : -INFINITY;
                     mx = fmaxf(mx, sc[hb][cb][x]);
                 }
-            const float rowmax = dec_hgroup_max(mx);
+            const float rowmax = qgroup_reduce_max(mx);
             // every tile holds at least one key < kend, so mnew is finite
             // unless a score itself is -inf; the guard covers that
             float mnew = fmaxf(m_run[hb], rowmax * scale2);
@@ -291,7 +262,7 @@ __global__ void __launch_bounds__(DEC_WAVES * 64, 2) fa_decode_kernel(
     constexpr int REC_M = HB * DCH * 4;
 #pragma unroll
     for (int hb = 0; hb < HB; ++hb) {
-        const float l_head = dec_hgroup_sum(l_run[hb]);
+        const float l_head = qgroup_reduce_sum(l_run[hb]);
 #pragma unroll
         for (int dc = 0; dc < DCH; ++dc)
 #pragma unroll

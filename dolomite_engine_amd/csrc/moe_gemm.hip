@@ -19,11 +19,8 @@
 // images stride cols+16 (conflict-free b128 A/B-frag reads), transposed
 // images stride 96 with the (col>>3)^(3*(row>>3)&7) block swizzle.
 
-#include "common.h"
+#include "mfma_tiles.h"
 
-typedef __bf16 bf16x8m __attribute__((ext_vector_type(8)));
-typedef float f32x4m __attribute__((ext_vector_type(4)));
-#define MFMA16M(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
 // rm stride for 64-col images; TST/swizzle for transposed images
 #define MOE_RS 80
@@ -31,8 +28,8 @@ typedef float f32x4m __attribute__((ext_vector_type(4)));
 #define MSWZ(row, col) ((row) * MOE_TS + (((((col) >> 3) ^ ((3 * ((row) >> 3)) & 7)) << 3) | ((col) & 7)))
 #define MSWZ8(row, col0) ((row) * MOE_TS + (((((col0) >> 3) ^ ((3 * ((row) >> 3)) & 7)) << 3)))
 
-__device__ __forceinline__ bf16x8m moe_load8(const __bf16* p, bool valid) {
-    bf16x8m r = *(const bf16x8m*)(valid ? p : p);  // caller clamps pointer
+__device__ __forceinline__ bf16x8 moe_load8(const __bf16* p, bool valid) {
+    bf16x8 r = *(const bf16x8*)(valid ? p : p);  // caller clamps pointer
     if (!valid)
 #pragma unroll
         for (int e = 0; e < 8; ++e) r[e] = (__bf16)0.f;
@@ -65,7 +62,7 @@ __global__ void __launch_bounds__(256) moe_gemm_fwd_kernel(
 
     const __bf16* we = w + (int64_t)e * N * K;
 
-    f32x4m acc[4];
+    f32x4 acc[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) acc[cb] = {0.f, 0.f, 0.f, 0.f};
 
@@ -79,22 +76,22 @@ __global__ void __launch_bounds__(256) moe_gemm_fwd_kernel(
             {
                 const bool v = kin && (m0 + row) < r1;
                 const __bf16* p = x + (int64_t)(v ? m0 + row : r0) * K + (v ? k0 + kk : 0);
-                *(bf16x8m*)&Xl[row * MOE_RS + kk] = moe_load8(p, v);
+                *(bf16x8*)&Xl[row * MOE_RS + kk] = moe_load8(p, v);
             }
             {
                 const bool v = kin && (n0 + row) < N;
                 const __bf16* p = we + (int64_t)(v ? n0 + row : 0) * K + (v ? k0 + kk : 0);
-                *(bf16x8m*)&Wl[row * MOE_RS + kk] = moe_load8(p, v);
+                *(bf16x8*)&Wl[row * MOE_RS + kk] = moe_load8(p, v);
             }
         }
         __syncthreads();
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
-            bf16x8m af = *(const bf16x8m*)&Xl[(wave * 16 + lr) * MOE_RS + kc * 32 + lg * 8];
+            bf16x8 af = *(const bf16x8*)&Xl[(wave * 16 + lr) * MOE_RS + kc * 32 + lg * 8];
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
-                bf16x8m bf = *(const bf16x8m*)&Wl[(cb * 16 + lr) * MOE_RS + kc * 32 + lg * 8];
-                acc[cb] = MFMA16M(af, bf, acc[cb]);
+                bf16x8 bf = *(const bf16x8*)&Wl[(cb * 16 + lr) * MOE_RS + kc * 32 + lg * 8];
+                acc[cb] = MFMA16(af, bf, acc[cb]);
             }
         }
     }
@@ -139,7 +136,7 @@ __global__ void __launch_bounds__(256) moe_gemm_dgrad_kernel(
 
     const __bf16* we = w + (int64_t)e * N * K;
 
-    f32x4m acc[4];
+    f32x4 acc[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) acc[cb] = {0.f, 0.f, 0.f, 0.f};
 
@@ -151,13 +148,13 @@ __global__ void __launch_bounds__(256) moe_gemm_dgrad_kernel(
             {
                 const bool v = (m0 + row) < r1 && (nn0 + c8) < N;
                 const __bf16* p = dy + (int64_t)(v ? m0 + row : r0) * N + (v ? nn0 + c8 : 0);
-                *(bf16x8m*)&Dl[row * MOE_RS + c8] = moe_load8(p, v);
+                *(bf16x8*)&Dl[row * MOE_RS + c8] = moe_load8(p, v);
             }
             {
                 // W rows n = nn0+row, k chunk c8: scatter to [k][n] image
                 const bool v = (nn0 + row) < N && (k0 + c8) < K;
                 const __bf16* p = we + (int64_t)(v ? nn0 + row : 0) * K + (v ? k0 + c8 : 0);
-                bf16x8m w8 = moe_load8(p, v);
+                bf16x8 w8 = moe_load8(p, v);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) WT[MSWZ(c8 + t, row)] = w8[t];
             }
@@ -165,11 +162,11 @@ __global__ void __launch_bounds__(256) moe_gemm_dgrad_kernel(
         __syncthreads();
 #pragma unroll
         for (int nc = 0; nc < 2; ++nc) {
-            bf16x8m af = *(const bf16x8m*)&Dl[(wave * 16 + lr) * MOE_RS + nc * 32 + lg * 8];
+            bf16x8 af = *(const bf16x8*)&Dl[(wave * 16 + lr) * MOE_RS + nc * 32 + lg * 8];
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
-                bf16x8m bf = *(const bf16x8m*)&WT[MSWZ8(cb * 16 + lr, nc * 32 + lg * 8)];
-                acc[cb] = MFMA16M(af, bf, acc[cb]);
+                bf16x8 bf = *(const bf16x8*)&WT[MSWZ8(cb * 16 + lr, nc * 32 + lg * 8)];
+                acc[cb] = MFMA16(af, bf, acc[cb]);
             }
         }
     }
@@ -207,7 +204,7 @@ __global__ void __launch_bounds__(256) moe_gemm_wgrad_kernel(
     __bf16* DT = (__bf16*)smem_raw;      // [64 n][MOE_TS] (dY^T image, swizzled)
     __bf16* XT = DT + 64 * MOE_TS;       // [64 k][MOE_TS] (X^T image, swizzled)
 
-    f32x4m acc[4];
+    f32x4 acc[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) acc[cb] = {0.f, 0.f, 0.f, 0.f};
 
@@ -220,14 +217,14 @@ __global__ void __launch_bounds__(256) moe_gemm_wgrad_kernel(
             {
                 const bool v = tin && (n0 + c8) < N;
                 const __bf16* p = dy + (int64_t)(v ? t0 + trow : r0) * N + (v ? n0 + c8 : 0);
-                bf16x8m d8 = moe_load8(p, v);
+                bf16x8 d8 = moe_load8(p, v);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) DT[MSWZ(c8 + t, trow)] = d8[t];
             }
             {
                 const bool v = tin && (k0 + c8) < K;
                 const __bf16* p = x + (int64_t)(v ? t0 + trow : r0) * K + (v ? k0 + c8 : 0);
-                bf16x8m x8 = moe_load8(p, v);
+                bf16x8 x8 = moe_load8(p, v);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) XT[MSWZ(c8 + t, trow)] = x8[t];
             }
@@ -235,11 +232,11 @@ __global__ void __launch_bounds__(256) moe_gemm_wgrad_kernel(
         __syncthreads();
 #pragma unroll
         for (int tc = 0; tc < 2; ++tc) {
-            bf16x8m af = *(const bf16x8m*)&DT[MSWZ8(wave * 16 + lr, tc * 32 + lg * 8)];
+            bf16x8 af = *(const bf16x8*)&DT[MSWZ8(wave * 16 + lr, tc * 32 + lg * 8)];
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
-                bf16x8m bf = *(const bf16x8m*)&XT[MSWZ8(cb * 16 + lr, tc * 32 + lg * 8)];
-                acc[cb] = MFMA16M(af, bf, acc[cb]);
+                bf16x8 bf = *(const bf16x8*)&XT[MSWZ8(cb * 16 + lr, tc * 32 + lg * 8)];
+                acc[cb] = MFMA16(af, bf, acc[cb]);
             }
         }
     }
@@ -316,14 +313,14 @@ __global__ void __launch_bounds__(256) moe_rows_combine_kernel(
     float acc[8] = {};
     for (int j = 0; j < k_top; ++j) {
         int64_t s = inv[t * k_top + j];
-        bf16x8m v = __builtin_nontemporal_load((const bf16x8m*)(h + s * K + c0));
+        bf16x8 v = __builtin_nontemporal_load((const bf16x8*)(h + s * K + c0));
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
     }
-    bf16x8m o;
+    bf16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (__bf16)acc[e];
-    __builtin_nontemporal_store(o, (bf16x8m*)(out + t * K + c0));
+    __builtin_nontemporal_store(o, (bf16x8*)(out + t * K + c0));
 }
 
 extern "C" int dolomite_moe_rows_combine(dolomite_stream_t stream, const void* h,
