@@ -12,7 +12,9 @@ modeling_utils/attention/*). Three attention implementations:
     same flash kernels in place on the padded buffer, one row span per
     batch row — no (B, S, S) bias, no unpad / pad copies. This path also
     generates: a preallocated KVCache, the single-token decode attention
-    kernel and GPTDolomiteForCausalLM.generate.
+    kernel, the extend kernel (several new tokens on a non-empty cache:
+    chunked prefill, continued conversations, draft verification) and
+    GPTDolomiteForCausalLM.generate.
 
 Forward signature, list-input handling, loss semantics (boundary drops) and
 state-dict names match the reference exactly (drop-in boundary).
@@ -30,6 +32,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 from ..ops import (
     QKVLayout,
     decode_attention,
+    extend_attention,
     fused_cross_entropy,
     fused_layernorm,
     fused_rmsnorm,
@@ -258,11 +261,16 @@ class KVCache:
     device, the keys stored per sequence. next_position: (B,) int64 on the
     device, the position id the next token of each sequence gets.
     get_seq_length() is the longest sequence as a host int, tracked on the
-    host without a readback."""
+    host without a readback. multi_token=True lets a forward put several new
+    tokens per sequence on a non-empty cache (the extend step: chunked
+    prefill, a continued conversation, draft verification); without it only
+    one token per step is accepted there."""
 
-    def __init__(self, config: GPTDolomiteConfig, batch_size: int, max_length: int, dtype, device):
+    def __init__(self, config: GPTDolomiteConfig, batch_size: int, max_length: int, dtype, device,
+                 multi_token: bool = False):
         self.batch_size = int(batch_size)
         self.max_length = int(max_length)
+        self.multi_token = bool(multi_token)
         shape = (self.batch_size, self.max_length, config.num_key_value_heads, config.head_dim)
         self.k = [torch.empty(shape, dtype=dtype, device=device) for _ in range(config.n_layer)]
         self.v = [torch.empty(shape, dtype=dtype, device=device) for _ in range(config.n_layer)]
@@ -278,13 +286,16 @@ class _LayerKV(NamedTuple):
     """What one attention layer needs of the cache for one forward: prefill
     appends the spans at dst_pos = 0 (cache_len None); a decode step appends
     one row per sequence at dst_pos = lengths and attends over cache_len =
-    lengths + 1 keys, at most max_len of them."""
+    lengths + 1 keys, at most max_len of them; an extend step (extend True)
+    appends each span at dst_pos = lengths and attends its rows causally
+    over cache_len = lengths + count keys."""
 
     k: torch.Tensor
     v: torch.Tensor
     dst_pos: torch.Tensor
     cache_len: torch.Tensor | None
     max_len: int
+    extend: bool = False
 
 
 # ---------------------------------------------------------------------------
@@ -376,7 +387,8 @@ class Attention(nn.Module):
         attention output are zero (pad_input's semantics). With a cache
         (kv): prefill additionally copies the spans' RoPE'd K/V into it; a
         decode step (S = 1, spans = one row each) appends its row and runs
-        the decode kernel over the cache in place of the causal kernels."""
+        the decode kernel over the cache in place of the causal kernels; an
+        extend step appends its spans and runs the extend kernel."""
         B, S, _ = hidden_states.shape
         seq_begin, seq_end, max_seqlen = spans
         qkv = self.c_attn(hidden_states.reshape(B * S, -1))  # (B*S, row_len)
@@ -386,9 +398,15 @@ class Attention(nn.Module):
         if kv is not None:
             kv_cache_append(qkv, self.layout, seq_begin, seq_end, kv.k, kv.v, kv.dst_pos, max_rows=max_seqlen)
             if kv.cache_len is not None:
-                attn_output = decode_attention(
-                    qkv, self.layout, kv.k, kv.v, kv.cache_len, self.softmax_scale, kv.max_len
-                )
+                if kv.extend:
+                    attn_output = extend_attention(
+                        qkv, self.layout, seq_begin, seq_end, max_seqlen, kv.k, kv.v, kv.cache_len,
+                        self.softmax_scale, kv.max_len,
+                    )
+                else:
+                    attn_output = decode_attention(
+                        qkv, self.layout, kv.k, kv.v, kv.cache_len, self.softmax_scale, kv.max_len
+                    )
                 return self.resid_dropout(self.c_proj(attn_output.view(B, S, -1)))
         attn_output = span_attention(
             qkv, seq_begin, seq_end, max_seqlen, self.layout, self.softmax_scale,
@@ -749,6 +767,18 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
         and the contiguity check (the reference's get_unpad_data also takes
         one .item()); a row with a hole raises — the flash kernels are causal
         over one contiguous run and there is no silent fallback."""
+        spans = self.dense_flash_spans(attention_mask, B, S, device)
+        rope_cos_sin = None
+        if self.position_embedding_type == "rope":
+            cos, sin = self.rope(S, device)  # (S, D) fp32
+            # same table rounding as the padding-free path
+            pos = position_ids.reshape(-1)
+            rope_cos_sin = (cos.to(dtype).float()[pos].contiguous(), sin.to(dtype).float()[pos].contiguous())
+        return spans, rope_cos_sin
+
+    @staticmethod
+    def dense_flash_spans(attention_mask, B: int, S: int, device):
+        """The (seq_begin, seq_end, max_seqlen) half of dense_flash_inputs."""
         assert B * S < 2**31, "row indices are int32"
         row0 = torch.arange(B, dtype=torch.int64, device=device) * S
         if attention_mask is None:
@@ -770,15 +800,7 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
                 )
             seq_begin = row0 + first
             seq_end = seq_begin + count
-        spans = (seq_begin.to(torch.int32), seq_end.to(torch.int32), int(max_seqlen))
-
-        rope_cos_sin = None
-        if self.position_embedding_type == "rope":
-            cos, sin = self.rope(S, device)  # (S, D) fp32
-            # same table rounding as the padding-free path
-            pos = position_ids.reshape(-1)
-            rope_cos_sin = (cos.to(dtype).float()[pos].contiguous(), sin.to(dtype).float()[pos].contiguous())
-        return spans, rope_cos_sin
+        return seq_begin.to(torch.int32), seq_end.to(torch.int32), int(max_seqlen)
 
     # ---- dense flash_attention_2 with a KV cache: prefill or one decode step ----
     def _embed(self, input_ids, position_ids, token_type_ids):
@@ -798,8 +820,13 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
         Decode (cache non-empty; S == 1): append at dst_pos = lengths, then
         decode_attention over lengths + 1 keys. position_ids of a decode
         step default to cache.next_position, which continues whatever
-        positions the prefill used. Every length check is on the host-side
-        length, before anything is launched."""
+        positions the prefill used. Extend (cache non-empty and created with
+        multi_token=True; S > 1, or S == 1 with a (B, 1) mask, whose pads
+        the decode step would take for tokens; mask None or one contiguous
+        run per row, an all-pad row included): append each run at dst_pos = lengths, then
+        extend_attention over lengths + count keys; position_ids default to
+        next_position + the index within the run. Every length check is on
+        the host-side length, before anything is launched."""
         B, S = input_ids.shape
         device = input_ids.device
         dtype = self.wte.weight.dtype
@@ -833,12 +860,45 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
                 count > 0, position_ids.reshape(-1)[last].long() + 1, torch.zeros_like(last)
             )
             cache._seq_length = max_seqlen
-        else:  # ---- one decode step ----
-            if S != 1:
+        elif S > 1 or (cache.multi_token and attention_mask is not None and tuple(attention_mask.shape) == (B, 1)):
+            # ---- extend: several new tokens on a non-empty cache (or a
+            # one-column chunk whose (B, 1) mask may hold pads, which the
+            # decode step below would take for tokens) ----
+            if not cache.multi_token:
                 raise NotImplementedError(
                     f"{S} new tokens on a non-empty KV cache (chunked prefill / speculative verify) "
-                    "is not built: decode one token per step"
+                    "need a cache created with KVCache(..., multi_token=True); without the flag, "
+                    "decode one token per step"
                 )
+            seq_begin, seq_end, max_run = self.dense_flash_spans(attention_mask, B, S, device)
+            count = seq_end - seq_begin
+            if position_ids is None:
+                # next_position + index within the run; pad columns repeat the run's ends
+                first = seq_begin.long() - torch.arange(B, dtype=torch.int64, device=device) * S
+                idx = torch.arange(S, dtype=torch.int64, device=device).unsqueeze(0) - first.unsqueeze(1)
+                idx = torch.minimum(idx.clamp(min=0), (count.long() - 1).clamp(min=0).unsqueeze(1))
+                position_ids = cache.next_position.unsqueeze(1) + idx
+            elif tuple(position_ids.shape) != (B, S):
+                raise ValueError(f"position_ids of an extend step must be (B, S) = {(B, S)}, got {tuple(position_ids.shape)}")
+            hs = self._embed(input_ids, position_ids, token_type_ids)
+            rope_cos_sin = None
+            if self.position_embedding_type == "rope":
+                cos, sin = self.rope(max(cache.max_length, self.rope.max_seq_len_cached), device)
+                pos = position_ids.reshape(-1)
+                rope_cos_sin = (cos.to(dtype).float()[pos].contiguous(), sin.to(dtype).float()[pos].contiguous())
+            spans = (seq_begin, seq_end, max_run)
+            new_len = cache.lengths + count
+            for i, block in enumerate(self.h):
+                kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + max_run, True)
+                hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
+            cache.lengths = new_len
+            # position id of each sequence's last real token + 1, unchanged for an all-pad row
+            last = (seq_end.long() - 1).clamp_(min=0)
+            cache.next_position = torch.where(
+                count > 0, position_ids.reshape(-1)[last].long() + 1, cache.next_position
+            )
+            cache._seq_length = past + max_run
+        else:  # ---- one decode step ----
             if attention_mask is not None and tuple(attention_mask.shape) not in ((B, 1), (B, past + 1)):
                 raise ValueError(
                     f"attention_mask of a decode step must be (B, 1) or (B, past + 1) = {(B, past + 1)}, "
@@ -1056,6 +1116,8 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
         eos_token_id: int | None = None,
         pad_token_id: int | None = None,
         generator: torch.Generator | None = None,
+        prefill_chunk_size: int | None = None,
+        past_key_values: KVCache | None = None,
     ):
         """Greedy or sampled continuation of a padded (B, S) prompt batch on
         the dense flash_attention_2 path: one prefill into a KVCache of
@@ -1066,6 +1128,15 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
         (default: eos); the loop stops when every sequence has finished (one
         host readback per step). Returns (B, S + n) ids, prompt included; the
         new tokens sit in columns S.. for either padding side.
+
+        prefill_chunk_size: prefill the prompt in column chunks of that many
+        tokens (the first through the prefill branch, the rest as extend
+        steps), so activation memory is bounded by the chunk; only the (B, h)
+        hidden row of each sequence's last real token is kept across chunks.
+        past_key_values: a caller's KVCache. Non-empty (it must have been
+        created with multi_token=True) the prompt CONTINUES the cached
+        conversation, in one extend step or in chunks; the cache needs room
+        for S + max_new_tokens more positions.
 
         This is a plain loop, deliberately NOT transformers' GenerationMixin:
         the transformers-5 Cache contract is not implemented, KVCache is the
@@ -1078,13 +1149,42 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
         device = input_ids.device
         if pad_token_id is None:
             pad_token_id = eos_token_id
-        cache = KVCache(self.config, B, S + max_new_tokens, self.transformer.wte.weight.dtype, device)
-        out = self.transformer(input_ids, past_key_values=cache, attention_mask=attention_mask, use_cache=True)
-        if attention_mask is None:
-            hidden = out.last_hidden_state[:, -1]
-        else:
-            last = S - 1 - (attention_mask.to(device) != 0).to(torch.int8).flip(-1).argmax(-1)
-            hidden = out.last_hidden_state[torch.arange(B, device=device), last]
+        if prefill_chunk_size is not None and prefill_chunk_size < 1:
+            raise ValueError("prefill_chunk_size must be >= 1")
+        cache = past_key_values
+        if cache is None:
+            cache = KVCache(self.config, B, S + max_new_tokens, self.transformer.wte.weight.dtype, device,
+                            multi_token=prefill_chunk_size is not None)
+        elif not isinstance(cache, KVCache):
+            raise TypeError(f"past_key_values must be a KVCache, got {type(cache).__name__}")
+        elif cache.get_seq_length() + S + max_new_tokens > cache.max_length:
+            raise ValueError(
+                f"KV cache overflow: {cache.get_seq_length()} cached + {S} prompt + {max_new_tokens} new tokens "
+                f"exceed max_length = {cache.max_length}"
+            )
+        # a fresh cache gets the column indices of the unchunked prefill as
+        # positions; a continued one continues cache.next_position
+        continued = cache.get_seq_length() > 0
+        chunk = S if prefill_chunk_size is None else int(prefill_chunk_size)
+        rows = torch.arange(B, device=device)
+        last = None
+        if attention_mask is not None:
+            attention_mask = attention_mask.to(device)
+            last = S - 1 - (attention_mask != 0).to(torch.int8).flip(-1).argmax(-1)
+        hidden = None  # (B, h): each sequence's last real row, wherever its chunk was
+        for a in range(0, S, chunk):
+            e = min(a + chunk, S)
+            pos = None if continued else torch.arange(a, e, device=device).unsqueeze(0).expand(B, -1)
+            out = self.transformer(
+                input_ids[:, a:e], past_key_values=cache, position_ids=pos, use_cache=True,
+                attention_mask=None if attention_mask is None else attention_mask[:, a:e],
+            ).last_hidden_state
+            if last is None:
+                hidden = out[:, -1]
+            else:
+                here = out[rows, (last - a).clamp(0, e - a - 1)]
+                inside = ((last >= a) & (last < e)).unsqueeze(1)
+                hidden = torch.where(inside, here, torch.zeros_like(here) if hidden is None else hidden)
 
         finished = torch.zeros(B, dtype=torch.bool, device=device)
         new_tokens = []

@@ -7,6 +7,8 @@ from .functional import (
     decode_attention,
     decode_num_splits,
     draw_attention_dropout_seed,
+    extend_attention,
+    extend_num_splits,
     fused_cross_entropy,
     fused_layernorm,
     fused_rmsnorm,

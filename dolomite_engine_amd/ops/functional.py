@@ -811,6 +811,98 @@ def decode_attention(qkv, layout: QKVLayout, k_cache, v_cache, cache_len, scale:
     return o.reshape(B, lo.H * lo.D).to(qkv.dtype)
 
 
+EXTEND_COLUMN_TILE = 128      # (query, q head) columns per workgroup of the extend kernel
+
+
+def extend_num_splits(batch: int, layout: QKVLayout, max_new: int, max_len: int) -> int:
+    """The split count extend_attention picks for num_splits=None:
+    decode_num_splits' rule on the extend kernel's workgroup count."""
+    tiles = -(-max(int(max_len), 1) // DECODE_KEY_TILE)
+    base = max(batch, 1) * layout.Hkv * max(-(-int(max_new) * layout.G // EXTEND_COLUMN_TILE), 1)
+    return max(1, min(-(-_DECODE_TARGET_WORKGROUPS // base), -(-tiles // 4)))
+
+
+def extend_attention(qkv, layout: QKVLayout, seq_begin, seq_end, max_new: int, k_cache, v_cache, cache_len,
+                     scale: float, max_len: int, num_splits: int | None = None):
+    """Causal attention of SEVERAL new tokens per sequence over its cached
+    keys: chunked prefill, the next turn of a cached conversation, the verify
+    pass over draft tokens. qkv: (T, row_len) packed rows; sequence b's new
+    tokens are rows [seq_begin[b], seq_end[b]), n_b >= 0 of them (only the q
+    slots are read; their K/V are already in the cache, appended at
+    dst_pos = cache_len - n_b). seq_begin / seq_end / cache_len: (B,) int32 on
+    qkv's device, spans ascending and disjoint. k_cache / v_cache:
+    (B, S_cap, Hkv, D). cache_len counts the valid keys INCLUDING the new
+    tokens: with past_b = cache_len[b] - n_b, query i attends keys
+    [0, past_b + i + 1) — the bottom-right-aligned causal mask. Whatever lies
+    behind cache_len[b] is ignored. max_new: host upper bound on n_b;
+    max_len: host upper bound on cache_len, <= S_cap. Returns (T, H*D) with
+    zeros on the rows outside every span.
+
+    num_splits: workgroups along the keys, combined in ascending split order
+    (bitwise reproducible). None picks, with
+    base = B * Hkv * ceil(max_new * G / 128) workgroups,
+        min(ceil(512 / base), ceil(ceil(max_len / 64) / 4))
+    (at least 1), the decode rule. Inference only: no backward."""
+    lo = layout
+    _no_grad_inputs("extend_attention", qkv, k_cache, v_cache)
+    _check_cache(lo, k_cache, v_cache)
+    B, S_cap = k_cache.shape[:2]
+    if qkv.dim() != 2 or qkv.shape[1] != lo.row_len or qkv.dtype != k_cache.dtype:
+        raise ValueError("qkv must be (T, row_len) in the cache dtype")
+    for name, t in (("seq_begin", seq_begin), ("seq_end", seq_end), ("cache_len", cache_len)):
+        if t.dtype != torch.int32 or t.shape != (B,):
+            raise TypeError(f"{name} must be an int32 tensor of shape ({B},)")
+    T = qkv.shape[0]
+    max_new, max_len = int(max_new), int(max_len)
+    if not 0 <= max_new <= T:
+        raise ValueError(f"max_new {max_new} outside [0, T = {T}]")
+    if not 0 <= max_len <= S_cap:
+        raise ValueError(f"max_len {max_len} outside [0, S_cap = {S_cap}]")
+    if not scale > 0:
+        raise ValueError("scale must be > 0")
+    nsplit = extend_num_splits(B, lo, max_new, max_len) if num_splits is None else int(num_splits)
+    if nsplit < 1:
+        raise ValueError("num_splits must be >= 1")
+    if qkv.is_cuda:
+        qkv = qkv.contiguous()
+        o = torch.empty(T, lo.H * lo.D, dtype=qkv.dtype, device=qkv.device)
+        scratch = None
+        if nsplit > 1:
+            n = hip.lib().dolomite_fa_extend_scratch_floats(B, max_new, lo.H, lo.D, nsplit)
+            scratch = torch.empty(n, dtype=torch.float32, device=qkv.device)
+        with hip.prof("fa_extend"):
+            hip.check(
+                hip.lib().dolomite_fa_extend(
+                    hip.stream(), hip.ptr(qkv), hip.ptr(k_cache), hip.ptr(v_cache), hip.ptr(o),
+                    hip.ptr(scratch), hip.ptr(seq_begin), hip.ptr(seq_end), hip.ptr(cache_len),
+                    B, max_new, T, lo.H, lo.Hkv, lo.D, lo.G, max_len, nsplit,
+                    lo.row_len, lo.q_gstride,
+                    k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+                    v_cache.stride(0), v_cache.stride(1), v_cache.stride(2),
+                    float(scale), hip.dt(qkv),
+                ),
+                "fa_extend",
+            )
+        return o
+    # CPU restatement: fp32 math, one sequence at a time
+    q, _, _ = lo.unpack_cpu(qkv)
+    G = lo.H // lo.Hkv
+    o = torch.zeros(T, lo.H, lo.D, dtype=torch.float32)
+    for b, (s, e, length) in enumerate(zip(seq_begin.tolist(), seq_end.tolist(), cache_len.tolist())):
+        n = min(e - s, max_new)
+        length = min(max(length, 0), max_len)
+        past = length - n
+        if n <= 0 or past < 0:
+            continue
+        kb = k_cache[b, :length].float().repeat_interleave(G, dim=1)  # (length, H, D)
+        vb = v_cache[b, :length].float().repeat_interleave(G, dim=1)
+        sc = torch.einsum("ihd,nhd->hin", q[s : s + n].float(), kb) * scale
+        seen = torch.arange(length)[None, :] <= past + torch.arange(n)[:, None]
+        p = torch.softmax(sc.masked_fill(~seen, float("-inf")), dim=-1)
+        o[s : s + n] = torch.einsum("hin,nhd->ihd", p, vb)
+    return o.reshape(T, lo.H * lo.D).to(qkv.dtype)
+
+
 # ---------------------------------------------------------------------------
 # Fused cross entropy (mean over non-ignored rows)
 # ---------------------------------------------------------------------------

@@ -376,6 +376,63 @@ int dolomite_fa_decode(dolomite_stream_t stream,
                        int64_t v_bstride, int64_t v_tstride, int64_t v_hstride,
                        float scale, int dtype);
 
+/* dolomite_fa_extend: n_b >= 0 new query tokens per sequence against the
+ * cache, causally (a continued conversation, a chunk of a chunked prefill,
+ * the verify pass over draft tokens). The new tokens are rows
+ * [seq_begin[b], seq_end[b]) of the packed qkv (T rows), n_b of them, and
+ * the cache ALREADY holds their K/V (the append has run with
+ * dst_pos = cache_len - n_b). With past_b = cache_len[b] - n_b, query i
+ * attends keys [0, past_b + i + 1): the bottom-right-aligned causal mask.
+ *   q[t, h, d] = qkv + t*q_tstride + (h/G)*q_gstride + (h%G)*D + d
+ *   seq_begin, seq_end: (batch,) int32 device pointers, ascending and
+ *     disjoint, 0 <= seq_begin[b] <= seq_end[b] <= T.
+ *   max_new: an upper bound on n_b (grid sizing; queries beyond it are not
+ *     computed).
+ *   cache_len: (batch,) int32 device pointer, the valid keys of each
+ *     sequence INCLUDING the new tokens; max_len bounds it, <= the cache
+ *     capacity.
+ *   o: (T, H*D) bf16 row-major contiguous; row t of a span gets query
+ *     t - seq_begin[b]. Rows outside every span (an empty span has none) are
+ *     all-(+0), written by dolomite_fa_zero_gap_rows from inside this call.
+ * Keys at and beyond cache_len[b] never influence the result, whatever that
+ * memory holds (NaN and Inf included); keys of later queries of the same
+ * chunk are masked exactly. Every value read from the device arrays is
+ * clamped (cache_len into [0, max_len], past_b >= 0, n_b <= max_new, the
+ * span into [0, T]): with arguments that break the preconditions the result
+ * is unspecified, but nothing outside qkv / o / the first max_len cache
+ * positions is touched.
+ *
+ * Work split: for one (sequence, kv head) the n_b*G (query, q head) pairs
+ * are flattened query-major, r = i*G + g, and a workgroup owns 128
+ * consecutive r, which share one pass over the kv head's K/V. The grid is
+ * (nsplit, ceil(max_new*G / 128) * batch, Hkv). Split c of a workgroup owns
+ * keys [c*chunk, min((c+1)*chunk, kmax)), kmax the largest causal bound of
+ * its columns and chunk = ceil(max_len / nsplit) rounded up to the 64-key
+ * tile; a split without keys is legal. With nsplit > 1 the workgroups store
+ * fp32 partials exclusively into `scratch` and a second kernel combines them
+ * in ascending split order: no atomics, bitwise reproducible for fixed
+ * arguments.
+ *   scratch: dolomite_fa_extend_scratch_floats(batch, max_new, H, D, nsplit)
+ *     floats, 16-byte aligned, caller-owned (0 and may be NULL for
+ *     nsplit == 1; the query returns -1 for invalid arguments).
+ * Error codes, all returned before any launch: 9010 dtype != bf16, 9011
+ * D > 128, 9015 scale not > 0, 9041 D or a stride not a (positive) multiple
+ * of 8, 9042 negative / inconsistent sizes (H != Hkv*G included), 9043
+ * nsplit < 1 or a grid dimension over its limit, 9044 nsplit > 1 without
+ * scratch.
+ * ---------------------------------------------------------------------- */
+int64_t dolomite_fa_extend_scratch_floats(int batch, int max_new, int H, int D, int nsplit);
+int dolomite_fa_extend(dolomite_stream_t stream,
+                       const void* qkv, const void* k_cache, const void* v_cache, void* o,
+                       float* scratch, const int32_t* seq_begin, const int32_t* seq_end,
+                       const int32_t* cache_len,
+                       int batch, int max_new, int64_t T, int H, int Hkv, int D, int G,
+                       int max_len, int nsplit,
+                       int64_t q_tstride, int64_t q_gstride,
+                       int64_t k_bstride, int64_t k_tstride, int64_t k_hstride,
+                       int64_t v_bstride, int64_t v_tstride, int64_t v_hstride,
+                       float scale, int dtype);
+
 /* MFMA fragment-layout self-test: computes C = A(16x32) @ B(32x16) with the
  * compiled fragment mapping; host verifies against a CPU matmul.
  * A/B bf16 row-major contiguous, C fp32 row-major. */
