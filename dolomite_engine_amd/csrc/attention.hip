@@ -12,8 +12,9 @@
 //
 // Design (CDNA4-first):
 //   - MFMA v_mfma_f32_16x16x32_bf16 for both products; 64-wide waves.
-//   - forward: workgroup = 8 waves = 512 threads; q-tile 128 rows (16 per
-//     wave), k-tile 64 keys streamed through LDS as two row-major [key][d]
+//   - forward: workgroup = 8 waves = 512 threads over a 128-row q-tile, or
+//     4 waves over 64 rows (FaShape; 16 rows per wave either way); k-tile
+//     64 keys streamed through LDS as two row-major [key][d]
 //     images in natural row order (stride DPAD+16: the b128 row reads, the
 //     staging writes and the transpose reads are all conflict-free).
 //   - the score tile is computed TRANSPOSED, S^T = K*Q^T (K image row as
@@ -214,12 +215,77 @@ static inline bool drop_p_valid(float p_drop) { return p_drop >= 0.f && p_drop <
 // q on l & 15): 4 contiguous bf16 per lane and block, one 8-byte store.
 // ===========================================================================
 
+// Full-tile K/V staging of the 4-wave shape. The 8-wave kernels keep two
+// (key, d0) pieces per thread in 8 registers; at 256 threads that layout
+// would take up to 16 and push the kernels past the 96-VGPR bound. Here a
+// thread owns ONE 8-element column chunk and walks down the image RPP rows at
+// a time: one global offset per operand and one LDS offset per lane, the
+// per-pass step a wave-uniform global stride and a constant LDS displacement.
+// CPR chunks span a row (the next power of two >= DPAD / 8, so a thread's
+// column is a mask, not a division); lanes whose chunk starts at or past D
+// stay idle.
+template <int DPAD, int NT>
+struct FaRowStager {
+    static constexpr int S = FaKvLds<DPAD>::S;
+    static constexpr int CPR = DPAD <= 32 ? 4 : DPAD <= 64 ? 8 : 16;
+    static constexpr int RPP = NT / CPR, PASSES = 64 / RPP;
+    static_assert(CPR * 8 >= DPAD && PASSES * RPP == 64, "one pass set covers the 64-key image");
+    int koff, voff, lds;
+    bool active;
+
+    __device__ __forceinline__ FaRowStager(int D, int kvh, int64_t k_ts, int64_t k_hs, int64_t v_ts, int64_t v_hs) {
+        const int row = (int)threadIdx.x / CPR, d0 = ((int)threadIdx.x % CPR) * 8;
+        active = d0 < D;
+        koff = (int)(row * k_ts + kvh * k_hs) + d0;   // fits 32 bits
+        voff = (int)(row * v_ts + kvh * v_hs) + d0;
+        lds = row * S + d0;
+    }
+    // t0: global token of image row 0; all 64 rows are valid keys
+    __device__ __forceinline__ void stage(const __bf16* k, const __bf16* v, int64_t t0, int64_t k_ts, int64_t v_ts,
+                                          __bf16* Kw, __bf16* Vw) const {
+        if (active) {
+#pragma unroll
+            for (int j = 0; j < PASSES; ++j) {
+                *(bf16x8*)&Kw[lds + j * RPP * S] = *(const bf16x8*)(k + (t0 + j * RPP) * k_ts + koff);
+                *(bf16x8*)&Vw[lds + j * RPP * S] = *(const bf16x8*)(v + (t0 + j * RPP) * v_ts + voff);
+            }
+        }
+    }
+};
+
+// the 8-wave shape stages by pieces, inside the kernels
+struct FaNoRowStager {
+    __device__ __forceinline__ FaNoRowStager(int, int, int64_t, int64_t, int64_t, int64_t) {}
+    __device__ __forceinline__ void stage(const __bf16*, const __bf16*, int64_t, int64_t, int64_t, __bf16*,
+                                          __bf16*) const {}
+};
+
+// ===========================================================================
+// Workgroup shapes of the fwd / dq kernels: NW waves of 16 q rows each over
+// one 64-key K/V image pair.
+//   NW = 8: 512 threads, 128 q rows, (512, 4) bound -> 2 workgroups per CU.
+//   NW = 4: 256 threads,  64 q rows, (256, 5) bound (<= 96 VGPR) -> 5 per CU:
+//           the images are 28.7 KB at DPAD = 96, so five fit in 160 KB of LDS.
+// The per-lane arithmetic is the same for both; only how many q rows share
+// one staged K/V tile differs. fa_fwd_waves / fa_dq_waves pick per
+// instantiation.
+// ===========================================================================
+template <int NW>
+struct FaShape {
+    static_assert(NW == 8 || NW == 4, "8-wave 128-row or 4-wave 64-row workgroups");
+    static constexpr int NT = NW * 64;     // threads
+    static constexpr int ROWS = NW * 16;   // q rows per workgroup
+    static constexpr int WAVES_PER_SIMD = NW == 8 ? 4 : 5;
+    template <int DPAD>
+    using RowStager = std::conditional_t<NW == 4, FaRowStager<DPAD, NT>, FaNoRowStager>;
+};
+
 // ===========================================================================
 // Forward
 // ===========================================================================
 
-template <int DPAD, bool DROPOUT>
-__global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
+template <int DPAD, bool DROPOUT, int NW>
+__global__ void __launch_bounds__(FaShape<NW>::NT, FaShape<NW>::WAVES_PER_SIMD) fa_fwd_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     __bf16* __restrict__ o, float* __restrict__ lse,
     const int32_t* __restrict__ seq_begin, const int32_t* __restrict__ seq_end,
@@ -230,6 +296,8 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     constexpr int KCH = DPAD / 32;   // contraction chunks for QK^T
     constexpr int DCH = DPAD / 16;   // output row blocks of O^T
     constexpr int SK = FaKvLds<DPAD>::S;   // K/V LDS row stride (elems), conflict-free (mfma_tiles.h)
+    constexpr int NT = FaShape<NW>::NT, ROWS = FaShape<NW>::ROWS;
+    constexpr int STJ = NW == 8 ? 2 : 0;   // 8-wave staging pieces per thread; 4-wave: FaRowStager
 
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
@@ -240,12 +308,9 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     const int L = __builtin_amdgcn_readfirstlane(seq_end[b]) - s0;
     // heaviest tiles (largest qs -> most k-tiles) dispatch FIRST: in-order
     // dispatch otherwise schedules the long-pole causal workgroups last
-    // 8 waves x 16 rows = 128 q rows per workgroup: K/V staging and
-    // barriers amortize over twice the compute at the same per-wave
-    // register budget
-    const int ntile_seq = (L + 127) / 128;
+    const int ntile_seq = (L + ROWS - 1) / ROWS;
     if (tile_id >= ntile_seq) return;
-    const int qs = (ntile_seq - 1 - tile_id) * 128;
+    const int qs = (ntile_seq - 1 - tile_id) * ROWS;
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -261,9 +326,9 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     //       (T20) and issues some chunk DMAs under partial exec masks, so
     //       inactive lanes leave stale LDS in the image (flaky parity
     //       failures across runs; see git history for the full variant).
-    // The (512, 4) bound (<= 128 VGPR, 4 waves/SIMD) keeps 2 of these
-    // 8-wave workgroups on a CU: the co-resident workgroup already hides
-    // staging latency, so the single-buffer two-barrier schedule stays.
+    // The bound keeps 2 8-wave or 5 4-wave workgroups on a CU: the
+    // co-resident workgroups already hide staging latency, so the
+    // single-buffer two-barrier schedule stays.
     extern __shared__ char smem_raw[];             // FaKvLds<DPAD>::bytes(DROPOUT)
     __bf16* Klds = (__bf16*)smem_raw;              // [64 key][SK]
     __bf16* Vlds = Klds + 64 * SK;                 // [64 key][SK]
@@ -312,11 +377,11 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     unsigned aV0, aV1;
     fa_tr16_perm_bases(Vlds, SK, lane, aV0, aV1);
 
-    const int kend = min(L, qs + 128);
+    const int kend = min(L, qs + ROWS);
     const int ntiles = (kend + 63) / 64;
 
     if (D < DPAD) {  // pad columns zeroed once (see dkv note)
-        for (int pidx = threadIdx.x; pidx < 64 * (DPAD - D) / 8; pidx += 512) {
+        for (int pidx = threadIdx.x; pidx < 64 * (DPAD - D) / 8; pidx += NT) {
             int key = pidx / ((DPAD - D) / 8);
             int d0 = D + (pidx % ((DPAD - D) / 8)) * 8;
             bf16x8 z = {};
@@ -326,11 +391,12 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     }
 
     // tile-invariant staging piece coordinates (see dkv note)
-    int st_koff[2], st_voff[2];
-    int st_klds[2], st_vlds[2];
+    int st_koff[STJ + 1], st_voff[STJ + 1];   // [STJ] unused: no zero-length arrays
+    int st_klds[STJ + 1], st_vlds[STJ + 1];
+    const typename FaShape<NW>::template RowStager<DPAD> rows(D, kvh, k_ts, k_hs, v_ts, v_hs);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        int pidx = (int)threadIdx.x + j * 512;
+    for (int j = 0; j < STJ; ++j) {
+        int pidx = (int)threadIdx.x + j * NT;
         int pp = pidx < 64 * D / 8 ? pidx : 0;
         int key = pp / (D / 8);
         int d0 = (pp % (D / 8)) * 8;
@@ -342,7 +408,7 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
 
     // T5 static priority: the later-dispatched half of an 8-wave workgroup
     // loses VALU arbitration; one setprio for it, no per-cluster flips.
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
+    if (NW == 8 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
 
     constexpr int PIECES = 64 * DPAD / 8;  // 8-elem staging pieces
 
@@ -350,15 +416,16 @@ __global__ void __launch_bounds__(512, 4) fa_fwd_kernel(
     auto stage_direct = [&](int ks_, __bf16* Kw, __bf16* Vw) {
         if (ks_ + 64 <= kend) {
             const int64_t disp = (int64_t)(s0 + ks_);
+            if constexpr (NW == 4) rows.stage(k, v, disp, k_ts, v_ts, Kw, Vw);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if ((int)threadIdx.x + j * 512 < 64 * D / 8) {
+            for (int j = 0; j < STJ; ++j) {
+                if ((int)threadIdx.x + j * NT < 64 * D / 8) {
                     *(bf16x8*)&Kw[st_klds[j]] = *(const bf16x8*)(k + disp * k_ts + st_koff[j]);
                     *(bf16x8*)&Vw[st_vlds[j]] = *(const bf16x8*)(v + disp * v_ts + st_voff[j]);
                 }
             }
         } else {
-            for (int pidx = threadIdx.x; pidx < PIECES; pidx += 512) {
+            for (int pidx = threadIdx.x; pidx < PIECES; pidx += NT) {
                 int key = pidx / (DPAD / 8);
                 int d0 = (pidx % (DPAD / 8)) * 8;
                 bool kv_valid = (ks_ + key) < kend;
@@ -532,13 +599,27 @@ static int fa_select_kernel(const FaProblem& p, Launch launch) {
     return p.p_drop > 0.f ? by_dpad(std::true_type{}) : by_dpad(std::false_type{});
 }
 
+// Which workgroup shape each instantiation runs. The forward takes 4 waves
+// wherever it compiles to <= 96 VGPRs with no scratch under the (256, 5)
+// bound; dq does so at DPAD <= 64 only: dq<96, false> fits (96 VGPRs) but
+// measured slower than its 8-wave shape (profiles/attn_occupancy_ab_bench.txt;
+// resource lines: profiles/attn_occupancy_kernel_resources.txt).
+template <int DPAD, bool DROPOUT>
+constexpr int fa_fwd_waves = (DPAD <= 64 || (DPAD == 96 && !DROPOUT)) ? 4 : 8;
+template <int DPAD, bool DROPOUT>
+constexpr int fa_dq_waves = (DPAD == 32 || (DPAD == 64 && !DROPOUT)) ? 4 : 8;
+
 // grid.x = tiles of the longest sequence; shorter sequences' surplus
 // workgroups exit on the span-length check.
-static dim3 fa_grid(const FaProblem& p) { return dim3((p.max_seqlen + 127) / 128, p.batch, p.H); }
+static dim3 fa_grid(const FaProblem& p, int rows) {
+    return dim3((p.max_seqlen + rows - 1) / rows, p.batch, p.H);
+}
 
 template <int DPAD, bool DROPOUT>
 static int launch_fa_fwd(const FaProblem& p) {
-    hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT>), fa_grid(p), dim3(512), FaKvLds<DPAD>::bytes(DROPOUT),
+    using Shape = FaShape<fa_fwd_waves<DPAD, DROPOUT>>;
+    hipLaunchKernelGGL((fa_fwd_kernel<DPAD, DROPOUT, fa_fwd_waves<DPAD, DROPOUT>>), fa_grid(p, Shape::ROWS),
+                       dim3(Shape::NT), FaKvLds<DPAD>::bytes(DROPOUT),
                        (hipStream_t)p.stream, (const __bf16*)p.q, (const __bf16*)p.k, (const __bf16*)p.v,
                        (__bf16*)p.o, p.lse, p.seq_begin, p.seq_end, p.H, p.Hkv, p.D, p.G,
                        p.q_ts, p.q_gs, p.k_ts, p.k_hs, p.v_ts, p.v_hs, (int64_t)p.H * p.D, p.T, p.scale,
@@ -1020,9 +1101,10 @@ __global__ void __launch_bounds__(512, DPAD <= 96 ? 4 : 2) fa_bwd_dkv_kernel(
 // Occupancy bound: the dropout-free DPAD=128 variant already sits at the
 // 128-VGPR cap (4 spills); the mask words push the DROPOUT one to 10 spills
 // under that cap, so it alone takes the looser 1-workgroup/CU bound and
-// compiles spill-free. Every other instantiation keeps (512, 4).
-template <int DPAD, bool DROPOUT>
-__global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq_kernel(
+// compiles spill-free. Every other instantiation takes its shape's bound.
+template <int DPAD, bool DROPOUT, int NW>
+__global__ void __launch_bounds__(FaShape<NW>::NT, (NW == 8 && DROPOUT && DPAD > 96) ? 2 : FaShape<NW>::WAVES_PER_SIMD)
+fa_bwd_dq_kernel(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
     const __bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     __bf16* __restrict__ dqkv_q,
@@ -1033,6 +1115,8 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     uint32_t seed_lo, uint32_t seed_hi, uint32_t drop_thr, float drop_rp) {
     constexpr int KCH = DPAD / 32;
     constexpr int DCH = DPAD / 16;
+    constexpr int NT = FaShape<NW>::NT, ROWS = FaShape<NW>::ROWS;
+    constexpr int STJ = NW == 8 ? 2 : 0;   // 8-wave staging pieces per thread; 4-wave: FaRowStager
 
     int tile_id = blockIdx.x, b = blockIdx.y, h = blockIdx.z;
     xcd_remap_tile_bh(tile_id, b, h);
@@ -1042,10 +1126,10 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     // main loop (measured: the compiler otherwise spills pointer pairs)
     const int s0 = __builtin_amdgcn_readfirstlane(seq_begin[b]);
     const int L = __builtin_amdgcn_readfirstlane(seq_end[b]) - s0;
-    // 8 waves x 16 rows = 128 q rows per workgroup; heaviest tiles first
-    const int ntile_seq = (L + 127) / 128;
+    // NW waves x 16 rows per workgroup; heaviest tiles first
+    const int ntile_seq = (L + ROWS - 1) / ROWS;
     if (tile_id >= ntile_seq) return;
-    const int qs = (ntile_seq - 1 - tile_id) * 128;
+    const int qs = (ntile_seq - 1 - tile_id) * ROWS;
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -1104,7 +1188,7 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     }
 
     if (D < DPAD) {  // pad columns zeroed once (see dkv note)
-        for (int pidx = threadIdx.x; pidx < 64 * (DPAD - D) / 8; pidx += 512) {
+        for (int pidx = threadIdx.x; pidx < 64 * (DPAD - D) / 8; pidx += NT) {
             int key = pidx / ((DPAD - D) / 8);
             int d0 = D + (pidx % ((DPAD - D) / 8)) * 8;
             bf16x8 z = {};
@@ -1114,11 +1198,12 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
     }
 
     // tile-invariant staging piece coordinates (see dkv note)
-    int st_koff[2], st_voff[2];
-    int st_klds[2], st_vlds[2];
+    int st_koff[STJ + 1], st_voff[STJ + 1];   // [STJ] unused: no zero-length arrays
+    int st_klds[STJ + 1], st_vlds[STJ + 1];
+    const typename FaShape<NW>::template RowStager<DPAD> rows(D, kvh, k_ts, k_hs, v_ts, v_hs);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        int pidx = (int)threadIdx.x + j * 512;
+    for (int j = 0; j < STJ; ++j) {
+        int pidx = (int)threadIdx.x + j * NT;
         int pp = pidx < 64 * D / 8 ? pidx : 0;
         int key = pp / (D / 8);
         int d0 = (pp % (D / 8)) * 8;
@@ -1128,11 +1213,11 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
         st_vlds[j] = key * SQ + d0;
     }
 
-    const int kend_total = min(L, qs + 128);
+    const int kend_total = min(L, qs + ROWS);
     const int nkt = (kend_total + 63) / 64;
 
     // T5 static priority for the younger workgroup half (see dkv note)
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
+    if (NW == 8 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
 
     for (int kt = 0; kt < nkt; ++kt) {
         const int ks = kt * 64;
@@ -1142,15 +1227,16 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
             const int pieces = 64 * DPAD / 8;
             if (ks + 64 <= kend_total) {
                 const int64_t disp = (int64_t)(s0 + ks);
+                if constexpr (NW == 4) rows.stage(k, v, disp, k_ts, v_ts, Klds, Vlds);
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if ((int)threadIdx.x + j * 512 < 64 * D / 8) {
+                for (int j = 0; j < STJ; ++j) {
+                    if ((int)threadIdx.x + j * NT < 64 * D / 8) {
                         *(bf16x8*)&Klds[st_klds[j]] = *(const bf16x8*)(k + disp * k_ts + st_koff[j]);
                         *(bf16x8*)&Vlds[st_vlds[j]] = *(const bf16x8*)(v + disp * v_ts + st_voff[j]);
                     }
                 }
             } else {
-                for (int pidx = threadIdx.x; pidx < pieces; pidx += 512) {
+                for (int pidx = threadIdx.x; pidx < pieces; pidx += NT) {
                     int key = pidx / (DPAD / 8);
                     int d0 = (pidx % (DPAD / 8)) * 8;
                     bool valid = (ks + key) < kend_total;
@@ -1261,7 +1347,8 @@ __global__ void __launch_bounds__(512, (DROPOUT && DPAD > 96) ? 2 : 4) fa_bwd_dq
 
 template <int DPAD, bool DROPOUT>
 static int launch_fa_bwd(const FaProblem& p) {
-    const dim3 grid = fa_grid(p), block(512);
+    const dim3 grid = fa_grid(p, 128), block(512);
+    using DqShape = FaShape<fa_dq_waves<DPAD, DROPOUT>>;
     const hipStream_t stream = (hipStream_t)p.stream;
     const __bf16 *q = (const __bf16*)p.q, *k = (const __bf16*)p.k, *v = (const __bf16*)p.v;
     const __bf16* dout = (const __bf16*)p.dout;
@@ -1274,7 +1361,8 @@ static int launch_fa_bwd(const FaProblem& p) {
                        p.T, p.scale, seed_lo, seed_hi, thr, rp);
     int err = dol_last_error();
     if (err) return err;
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD, DROPOUT>), grid, block, FaKvLds<DPAD>::bytes(DROPOUT), stream,
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<DPAD, DROPOUT, fa_dq_waves<DPAD, DROPOUT>>), fa_grid(p, DqShape::ROWS),
+                       dim3(DqShape::NT), FaKvLds<DPAD>::bytes(DROPOUT), stream,
                        q, k, v, dout, p.lse, p.delta, (__bf16*)p.dqkv_q, p.seq_begin, p.seq_end,
                        p.H, p.Hkv, p.D, p.G, p.q_ts, p.q_gs, p.k_ts, p.k_hs, p.v_ts, p.v_hs, p.do_ts,
                        p.T, p.scale, seed_lo, seed_hi, thr, rp);
