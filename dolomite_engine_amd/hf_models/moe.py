@@ -15,6 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from transformers.modeling_outputs import MoeCausalLMOutputWithPast, MoeModelOutputWithPast
 
+from .. import ops
 from ..ops.functional import MoERowsCombine, MoERowsGather
 from .config import GPTDolomiteConfig
 from .modeling import (
@@ -122,21 +123,27 @@ class SparseMoE(nn.Module):
 
         # routing (base.py:96-106): top-k logits -> fp32 softmax over the k
         router_logits = self.gate(hidden_states)
-        router_weights, selected_experts = router_logits.topk(self.top_k, dim=-1)
-        router_weights = F.softmax(router_weights.float(), dim=-1).type_as(hidden_states)
+        # the fused HIP routing op (csrc/moe_route.hip): None on CPU and for
+        # the dtypes / expert counts it does not serve
+        routed = ops.moe_route(router_logits, self.top_k) if router_logits.dtype == hidden_states.dtype else None
+        if routed is not None:
+            batch_gates, batch_index, inv, num_tokens_per_expert, _ = routed
+        else:
+            router_weights, selected_experts = router_logits.topk(self.top_k, dim=-1)
+            router_weights = F.softmax(router_weights.float(), dim=-1).type_as(hidden_states)
 
-        # expert assignment (base.py:108-127): sort token-expert pairs by expert
-        selected_flat = selected_experts.flatten()
-        num_tokens_per_expert = selected_flat.bincount(minlength=self.num_experts)
-        _, index_sorted_experts = selected_flat.sort(0)
-        batch_index = index_sorted_experts // self.top_k
-        batch_gates = router_weights.flatten()[index_sorted_experts]
-        # inverse of the expert sort (inv[pair] = slot): lets the gather
-        # backward and the scatter-back run through the deterministic
-        # combine kernel instead of torch's atomic index_add
-        n_pairs = selected_flat.numel()
-        inv = torch.empty(n_pairs, dtype=torch.int32, device=hidden_states.device)
-        inv[index_sorted_experts] = torch.arange(n_pairs, dtype=torch.int32, device=hidden_states.device)
+            # expert assignment (base.py:108-127): sort token-expert pairs by expert
+            selected_flat = selected_experts.flatten()
+            num_tokens_per_expert = selected_flat.bincount(minlength=self.num_experts)
+            _, index_sorted_experts = selected_flat.sort(0)
+            batch_index = index_sorted_experts // self.top_k
+            batch_gates = router_weights.flatten()[index_sorted_experts]
+            # inverse of the expert sort (inv[pair] = slot): lets the gather
+            # backward and the scatter-back run through the deterministic
+            # combine kernel instead of torch's atomic index_add
+            n_pairs = selected_flat.numel()
+            inv = torch.empty(n_pairs, dtype=torch.int32, device=hidden_states.device)
+            inv[index_sorted_experts] = torch.arange(n_pairs, dtype=torch.int32, device=hidden_states.device)
 
         expert_inputs = MoERowsGather.apply(hidden_states, batch_index, inv, self.top_k)
         h = self.c_fc(expert_inputs, num_tokens_per_expert)

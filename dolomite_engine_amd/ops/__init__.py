@@ -14,6 +14,7 @@ from .functional import (
     fused_rmsnorm,
     grouped_expert_gemm,
     kv_cache_append,
+    moe_route,
     rope_packed_qkv,
     span_attention,
     varlen_attention,

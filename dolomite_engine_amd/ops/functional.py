@@ -1155,3 +1155,102 @@ def grouped_expert_gemm(x, weight, bias, num_tokens_per_expert):
     if max_rows == 0:
         return torch.zeros(x.shape[0], N, dtype=x.dtype, device=x.device)
     return GroupedExpertGemm.apply(x.contiguous(), weight, bias, offsets, max_rows)
+
+
+# ---------------------------------------------------------------------------
+# MoE routing (csrc/moe_route.hip) — replaces the torch chain of the
+# SparseMoE router (moe/base.py:96-127): topk, fp32 softmax over the selected
+# logits, bincount, the expert sort and the gather / index-put built on it.
+# ---------------------------------------------------------------------------
+
+MOE_ROUTE_MAX_EXPERTS = 64
+MOE_ROUTE_MAX_TOP_K = 8
+
+
+def _moe_route_ref(router_logits, top_k):
+    """The routing contract in plain torch (any device; what SparseMoE's
+    eager lines compute, with the tie rule made explicit): the top_k largest
+    logits of each token in descending order, equal logits to the lowest
+    expert index; gates = fp32 softmax over them, cast to the logits' dtype;
+    the (token, expert) pairs sorted by expert with a STABLE sort.
+    Returns (batch_gates, batch_index, inv, num_tokens_per_expert, selected)."""
+    E = router_logits.shape[-1]
+    # a stable descending sort keeps equal logits in ascending expert order
+    vals, idx = router_logits.sort(dim=-1, descending=True, stable=True)
+    vals, selected = vals[:, :top_k], idx[:, :top_k]
+    gates = torch.softmax(vals.float(), dim=-1).to(router_logits.dtype)
+    flat = selected.flatten()
+    num_tokens_per_expert = flat.bincount(minlength=E)
+    _, order = flat.sort(dim=0, stable=True)
+    n_pairs = flat.numel()
+    inv = torch.empty(n_pairs, dtype=torch.int32, device=flat.device)
+    inv[order] = torch.arange(n_pairs, dtype=torch.int32, device=flat.device)
+    return gates.flatten()[order], order // top_k, inv, num_tokens_per_expert, selected.to(torch.int32)
+
+
+class MoERoute(torch.autograd.Function):
+    """Three launches forward (top-k + gates + per-tile histogram, scan,
+    stable scatter), one backward; see include/dolomite_hip.h."""
+
+    @staticmethod
+    def forward(ctx, router_logits, top_k):
+        T, E = router_logits.shape
+        dev = router_logits.device
+        n_pairs = T * top_k
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        selected, inv, offsets = i32(T, top_k), i32(n_pairs), i32(E + 1)
+        gates = torch.empty(T, top_k, dtype=router_logits.dtype, device=dev)
+        batch_gates = torch.empty(n_pairs, dtype=router_logits.dtype, device=dev)
+        batch_index = torch.empty(n_pairs, dtype=torch.int64, device=dev)
+        if T == 0:
+            num_tokens_per_expert = torch.zeros(E, dtype=torch.int64, device=dev)
+        else:
+            num_tokens_per_expert = torch.empty(E, dtype=torch.int64, device=dev)
+            scratch = i32(hip.lib().dolomite_moe_route_scratch_ints(T, E, top_k))
+            with hip.prof("moe_route_fwd"):
+                hip.check(
+                    hip.lib().dolomite_moe_route_fwd(
+                        hip.stream(), hip.ptr(router_logits), hip.ptr(selected), hip.ptr(gates), hip.ptr(inv),
+                        hip.ptr(batch_index), hip.ptr(batch_gates), hip.ptr(num_tokens_per_expert),
+                        hip.ptr(offsets), hip.ptr(scratch), T, E, top_k, hip.dt(router_logits),
+                    ),
+                    "moe_route_fwd",
+                )
+        ctx.save_for_backward(router_logits, selected, inv)
+        ctx.top_k = top_k
+        ctx.mark_non_differentiable(batch_index, inv, num_tokens_per_expert, selected)
+        return batch_gates, batch_index, inv, num_tokens_per_expert, selected
+
+    @staticmethod
+    def backward(ctx, d_batch_gates, *_):
+        router_logits, selected, inv = ctx.saved_tensors
+        T, E = router_logits.shape
+        d_logits = torch.empty_like(router_logits)
+        d_batch_gates = d_batch_gates.to(router_logits.dtype).contiguous()
+        with hip.prof("moe_route_bwd"):
+            hip.check(
+                hip.lib().dolomite_moe_route_bwd(
+                    hip.stream(), hip.ptr(d_batch_gates), hip.ptr(inv), hip.ptr(selected),
+                    hip.ptr(router_logits), hip.ptr(d_logits), T, E, ctx.top_k, hip.dt(router_logits),
+                ),
+                "moe_route_bwd",
+            )
+        return d_logits, None
+
+
+def moe_route(router_logits, top_k):
+    """Route (T, E) router logits on the HIP kernels: returns (batch_gates,
+    batch_index, inv, num_tokens_per_expert, selected_experts) as
+    _moe_route_ref states them, or None when the kernels do not engage
+    (anything but CUDA bf16 / fp32 logits with E <= 64 and
+    top_k <= min(E, 8)), so the caller keeps its own path."""
+    if not router_logits.is_cuda or router_logits.dtype not in (torch.bfloat16, torch.float32):
+        return None
+    if router_logits.dim() != 2:
+        return None
+    E = router_logits.shape[1]
+    if not (1 <= E <= MOE_ROUTE_MAX_EXPERTS and 1 <= top_k <= min(E, MOE_ROUTE_MAX_TOP_K)):
+        return None
+    if router_logits.shape[0] * top_k >= 2**31:
+        return None
+    return MoERoute.apply(router_logits.contiguous(), int(top_k))

@@ -526,6 +526,54 @@ int dolomite_moe_gemm_wgrad(dolomite_stream_t stream, const void* dy, const void
                             int E, int N, int K, int dtype);
 
 /* ------------------------------------------------------------------------
+ * MoE token routing — replaces the torch chain of the SparseMoE router
+ * (moe/base.py:96-127): topk, fp32 softmax over the k selected logits,
+ * bincount, the expert sort, and the gather / index-put built on it.
+ *
+ * logits: (T, E) row-major, fp32 or bf16. 1 <= E <= 64,
+ * 1 <= top_k <= min(E, 8). With pair p = t*top_k + j:
+ *   selected[p]  int32: token t's j-th largest logit's expert (descending
+ *                logits; equal logits go to the LOWEST expert index)
+ *   gates[p]     softmax over the top_k selected logits of token t, evaluated
+ *                in fp32 and rounded once to the logits' dtype
+ *   inv[p]       int32: the pair's position ("slot") in the STABLE sort of
+ *                the pairs by expert (ascending p inside an expert)
+ *   batch_index[slot] = p / top_k (int64),  batch_gates[slot] = gates[p]
+ *   num_tokens_per_expert (E,) int64, offsets (E+1,) int32 its exclusive
+ *                cumulative sum (offsets[E] = T*top_k)
+ * i.e. what selected.flatten().sort(stable=True) gives. Three launches (top-k
+ * with a per-tile expert histogram, a scan, a rank-based scatter); no slot
+ * comes from an atomic counter: bitwise reproducible.
+ *   scratch: dolomite_moe_route_scratch_ints(T, E, top_k) int32, caller-owned
+ *     (ceil(T / 128) * E; the query returns -1 for invalid arguments). Need
+ *     not be cleared.
+ * T == 0 is legal and launches nothing. NaN logits: unspecified result,
+ * nothing outside the buffers is touched.
+ *
+ * dolomite_moe_route_bwd: given d_batch_gates (T*top_k,) in slot order (the
+ * logits' dtype), writes every element of d_logits (T, E), which need not be
+ * cleared: with w the fp32 softmax of token t's selected logits (recomputed
+ * from `logits` as the forward evaluated it, before rounding) and
+ * g_j = d_batch_gates[inv[t*top_k + j]],
+ *   d_logits[t, selected_j] = w_j * (g_j - sum_i w_i g_i),  +0 elsewhere.
+ * top_k == 1 gives exactly +0 everywhere. selected / inv values are clamped
+ * into range before use.
+ * Error codes, all returned before any launch: 9050 dtype not fp32 / bf16,
+ * 9051 E or top_k out of range, 9052 T < 0 or T*top_k >= 2^31, 9053 no
+ * scratch.
+ * ---------------------------------------------------------------------- */
+int64_t dolomite_moe_route_scratch_ints(int64_t T, int E, int top_k);
+int dolomite_moe_route_fwd(dolomite_stream_t stream, const void* logits,
+                           int32_t* selected, void* gates, int32_t* inv,
+                           int64_t* batch_index, void* batch_gates,
+                           int64_t* num_tokens_per_expert, int32_t* offsets,
+                           int32_t* scratch, int64_t T, int E, int top_k, int dtype);
+int dolomite_moe_route_bwd(dolomite_stream_t stream, const void* d_batch_gates,
+                           const int32_t* inv, const int32_t* selected,
+                           const void* logits, void* d_logits,
+                           int64_t T, int E, int top_k, int dtype);
+
+/* ------------------------------------------------------------------------
  * Host-side dataset index builders (CPU; the reference's only native
  * component, data/megatron/utils/helpers.cpp).
  * build_sample_idx: pack epoch-replicated documents into seq_length+1 token
