@@ -43,27 +43,6 @@
 #define DEC_WAVES 4      // waves per workgroup
 #define DEC_KTILE 64     // keys per wave step
 
-// One V^T A-fragment: two transpose reads of the row-major image in the
-// permuted key order of attention.hip "Swapped-operand score tiles". The
-// reads and their wait live in one asm block (see attention.hip): the step is
-// HBM-bound, so there is no lookahead and no use for the counted ladder of
-// mfma_tiles.h (moving the reads onto it changed every instantiation's code).
-template <int OFF>
-__device__ __forceinline__ bf16x8 dec_tr16_frag(unsigned a0, unsigned a1) {
-    bf16x4 lo, hi;
-    asm volatile(
-        "ds_read_b64_tr_b16 %0, %2 offset:%c4\n\t"
-        "ds_read_b64_tr_b16 %1, %3 offset:%c4\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(lo), "=&v"(hi)
-        : "v"(a0), "v"(a1), "i"(OFF)
-        : "memory");
-    bf16x8 out;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { out[t] = lo[t]; out[4 + t] = hi[t]; }
-    return out;
-}
-
 // Per-wave LDS region: the V image [64 key][DPAD+16] bf16 during the key
 // loop, then the wave's join record (fp32 O^T fragments, m, l). The image is
 // the larger of the two for every (DPAD, HB) instantiated.
@@ -360,6 +339,14 @@ __global__ void __launch_bounds__(64) fa_decode_combine_kernel(
     *(bf16x4*)&o[row * D + d0] = ov;
 }
 
+// Host side of the combine, shared with decode_fp8.hip (same partials).
+int dol_fa_decode_combine(hipStream_t s, const float* part_o, const float* part_m, const float* part_l,
+                          __bf16* o, int64_t rows, int D, int nsplit) {
+    hipLaunchKernelGGL(fa_decode_combine_kernel, dim3((unsigned)rows), dim3(64), 0, s,
+                       part_o, part_m, part_l, o, D, nsplit);
+    return dol_last_error();
+}
+
 extern "C" int64_t dolomite_fa_decode_scratch_floats(int batch, int H, int D, int nsplit) {
     if (batch < 0 || H < 0 || D < 0 || nsplit < 1) return -1;
     if (nsplit == 1) return 0;
@@ -389,9 +376,7 @@ static int launch_fa_decode(hipStream_t s, const __bf16* q, const __bf16* kc, co
                        q_ts, q_gs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale);
     int rc = dol_last_error();
     if (rc != 0 || nsplit == 1) return rc;
-    hipLaunchKernelGGL(fa_decode_combine_kernel, dim3((unsigned)(batch * H)), dim3(64), 0, s,
-                       part_o, part_m, part_l, o, D, nsplit);
-    return dol_last_error();
+    return dol_fa_decode_combine(s, part_o, part_m, part_l, o, (int64_t)batch * H, D, nsplit);
 }
 
 extern "C" int dolomite_fa_decode(dolomite_stream_t stream,

@@ -94,6 +94,33 @@ __device__ __forceinline__ void tr16_ladder(unsigned a0, unsigned a1, Off off, M
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// One V^T A-fragment of the decode kernels (decode.hip, decode_fp8.hip): two
+// transpose reads of the row-major image in the permuted key order of
+// attention.hip "Swapped-operand score tiles". The reads and their wait live
+// in one asm block (see attention.hip): the step is HBM-bound, so there is no
+// lookahead and no use for the counted ladder above (moving the reads onto it
+// changed every instantiation's code).
+template <int OFF>
+__device__ __forceinline__ bf16x8 dec_tr16_frag(unsigned a0, unsigned a1) {
+    bf16x4 lo, hi;
+    asm volatile(
+        "ds_read_b64_tr_b16 %0, %2 offset:%c4\n\t"
+        "ds_read_b64_tr_b16 %1, %3 offset:%c4\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(lo), "=&v"(hi)
+        : "v"(a0), "v"(a1), "i"(OFF)
+        : "memory");
+    bf16x8 out;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { out[t] = lo[t]; out[4 + t] = hi[t]; }
+    return out;
+}
+
+// Split combine of the decode kernels (defined in decode.hip): o[row] from
+// the fp32 partials of `rows` = batch*H rows, in ascending split order.
+int dol_fa_decode_combine(hipStream_t s, const float* part_o, const float* part_m, const float* part_l,
+                          __bf16* o, int64_t rows, int D, int nsplit);
+
 // Branchless guarded 16B load. Requires D % 8 == 0 (every head dim on this
 // path): a chunk is then fully inside [0, D) or fully in the pad, so the
 // guard reduces to ONE wave-divergent-free vector load from a clamped

@@ -41,6 +41,7 @@ from ..ops import (
     span_attention,
     varlen_attention,
 )
+from ..ops.functional import FP8_KV_DTYPE
 from .config import GPTDolomiteConfig
 
 
@@ -264,14 +265,34 @@ class KVCache:
     host without a readback. multi_token=True lets a forward put several new
     tokens per sequence on a non-empty cache (the extend step: chunked
     prefill, a continued conversation, draft verification); without it only
-    one token per step is accepted there."""
+    one token per step is accepted there.
+
+    kv_dtype="fp8" stores K/V as e4m3 with one fp32 scale per (position, kv
+    head): k[i], v[i] are torch.float8_e4m3fn and k_scale[i], v_scale[i]
+    (B, Hkv, max_length) fp32 (None lists otherwise) — half the bytes held and
+    half the bytes a decode step reads. The prefill still attends in bf16 from
+    the unquantised K/V; only the append quantises. On the GPU the model must
+    be bf16; the extend step (multi_token) has no fp8 kernel yet."""
 
     def __init__(self, config: GPTDolomiteConfig, batch_size: int, max_length: int, dtype, device,
-                 multi_token: bool = False):
+                 multi_token: bool = False, kv_dtype: str | None = None):
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got {kv_dtype!r}")
         self.batch_size = int(batch_size)
         self.max_length = int(max_length)
         self.multi_token = bool(multi_token)
+        self.kv_dtype = kv_dtype
         shape = (self.batch_size, self.max_length, config.num_key_value_heads, config.head_dim)
+        self.k_scale = self.v_scale = [None] * config.n_layer
+        if kv_dtype == "fp8":
+            if self.multi_token:
+                raise NotImplementedError("multi_token=True with an fp8 KV cache: the extend kernel is bf16-only")
+            if torch.device(device).type == "cuda" and dtype != torch.bfloat16:
+                raise TypeError(f"an fp8 KV cache on the GPU needs a bf16 model, got {dtype}")
+            dtype = FP8_KV_DTYPE
+            sshape = (self.batch_size, config.num_key_value_heads, self.max_length)
+            self.k_scale = [torch.empty(sshape, dtype=torch.float32, device=device) for _ in range(config.n_layer)]
+            self.v_scale = [torch.empty(sshape, dtype=torch.float32, device=device) for _ in range(config.n_layer)]
         self.k = [torch.empty(shape, dtype=dtype, device=device) for _ in range(config.n_layer)]
         self.v = [torch.empty(shape, dtype=dtype, device=device) for _ in range(config.n_layer)]
         self.lengths = torch.zeros(self.batch_size, dtype=torch.int32, device=device)
@@ -288,7 +309,8 @@ class _LayerKV(NamedTuple):
     one row per sequence at dst_pos = lengths and attends over cache_len =
     lengths + 1 keys, at most max_len of them; an extend step (extend True)
     appends each span at dst_pos = lengths and attends its rows causally
-    over cache_len = lengths + count keys."""
+    over cache_len = lengths + count keys. k_scale / v_scale: the layer's
+    scales of an fp8 cache, None otherwise."""
 
     k: torch.Tensor
     v: torch.Tensor
@@ -296,6 +318,8 @@ class _LayerKV(NamedTuple):
     cache_len: torch.Tensor | None
     max_len: int
     extend: bool = False
+    k_scale: torch.Tensor | None = None
+    v_scale: torch.Tensor | None = None
 
 
 # ---------------------------------------------------------------------------
@@ -396,7 +420,8 @@ class Attention(nn.Module):
             cos, sin = rope_cos_sin  # (B*S, D) fp32
             qkv = rope_packed_qkv(qkv, cos, sin, self.layout)
         if kv is not None:
-            kv_cache_append(qkv, self.layout, seq_begin, seq_end, kv.k, kv.v, kv.dst_pos, max_rows=max_seqlen)
+            kv_cache_append(qkv, self.layout, seq_begin, seq_end, kv.k, kv.v, kv.dst_pos, max_rows=max_seqlen,
+                            k_scale=kv.k_scale, v_scale=kv.v_scale)
             if kv.cache_len is not None:
                 if kv.extend:
                     attn_output = extend_attention(
@@ -405,7 +430,8 @@ class Attention(nn.Module):
                     )
                 else:
                     attn_output = decode_attention(
-                        qkv, self.layout, kv.k, kv.v, kv.cache_len, self.softmax_scale, kv.max_len
+                        qkv, self.layout, kv.k, kv.v, kv.cache_len, self.softmax_scale, kv.max_len,
+                        k_scale=kv.k_scale, v_scale=kv.v_scale,
                     )
                 return self.resid_dropout(self.c_proj(attn_output.view(B, S, -1)))
         attn_output = span_attention(
@@ -850,7 +876,7 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             seq_begin, seq_end, max_seqlen = spans
             dst_pos = torch.zeros(B, dtype=torch.int32, device=device)
             for i, block in enumerate(self.h):
-                kv = _LayerKV(cache.k[i], cache.v[i], dst_pos, None, 0)
+                kv = _LayerKV(cache.k[i], cache.v[i], dst_pos, None, 0, False, cache.k_scale[i], cache.v_scale[i])
                 hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
             count = seq_end - seq_begin
             cache.lengths.copy_(count)
@@ -918,7 +944,8 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             spans = (rows, rows + 1, 1)
             new_len = cache.lengths + 1
             for i, block in enumerate(self.h):
-                kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + 1)
+                kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + 1, False,
+                              cache.k_scale[i], cache.v_scale[i])
                 hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
             cache.lengths = new_len
             cache.next_position = position_ids.reshape(-1).long() + 1
@@ -1118,6 +1145,7 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
         generator: torch.Generator | None = None,
         prefill_chunk_size: int | None = None,
         past_key_values: KVCache | None = None,
+        kv_cache_dtype: str | None = None,
     ):
         """Greedy or sampled continuation of a padded (B, S) prompt batch on
         the dense flash_attention_2 path: one prefill into a KVCache of
@@ -1137,6 +1165,10 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
         created with multi_token=True) the prompt CONTINUES the cached
         conversation, in one extend step or in chunks; the cache needs room
         for S + max_new_tokens more positions.
+        kv_cache_dtype: None keeps K/V in the model dtype; "fp8" allocates
+        the cache as KVCache(..., kv_dtype="fp8") (a caller's cache keeps its
+        own kv_dtype; naming another one here is an error). Not with prefill_chunk_size: the
+        extend step has no fp8 kernel (NotImplementedError).
 
         This is a plain loop, deliberately NOT transformers' GenerationMixin:
         the transformers-5 Cache contract is not implemented, KVCache is the
@@ -1154,9 +1186,11 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
         cache = past_key_values
         if cache is None:
             cache = KVCache(self.config, B, S + max_new_tokens, self.transformer.wte.weight.dtype, device,
-                            multi_token=prefill_chunk_size is not None)
+                            multi_token=prefill_chunk_size is not None, kv_dtype=kv_cache_dtype)
         elif not isinstance(cache, KVCache):
             raise TypeError(f"past_key_values must be a KVCache, got {type(cache).__name__}")
+        elif kv_cache_dtype is not None and cache.kv_dtype != kv_cache_dtype:
+            raise ValueError(f"kv_cache_dtype = {kv_cache_dtype!r}, but the cache was created with {cache.kv_dtype!r}")
         elif cache.get_seq_length() + S + max_new_tokens > cache.max_length:
             raise ValueError(
                 f"KV cache overflow: {cache.get_seq_length()} cached + {S} prompt + {max_new_tokens} new tokens "

@@ -87,12 +87,17 @@ class ModelWrapper(nn.Module):
     def save_pretrained(self, path: str) -> None:
         self.model.save_pretrained(path, safe_serialization=True)
 
-    def generate(self, batch: dict, generate_kwargs: dict) -> tuple[torch.Tensor, list[int]]:
+    def generate(self, batch: dict, generate_kwargs: dict,
+                 kv_cache_dtype: str | None = None) -> tuple[torch.Tensor, list[int]]:
         """Reference model_wrapper/base.py:110-136 minus the tokenizer: the
         generated ids with the prompt trimmed, and the number of generated
-        tokens per sequence (non-eos tokens + 1 for the eos itself)."""
+        tokens per sequence (non-eos tokens + 1 for the eos itself).
+        kv_cache_dtype="fp8" generates over an e4m3 KV cache (the model's
+        generate argument of that name)."""
         if self.use_padding_free_transformer:
             raise NotImplementedError("padding free transformer doesn't support generation")
+        if kv_cache_dtype is not None:
+            generate_kwargs = {**generate_kwargs, "kv_cache_dtype": kv_cache_dtype}
         device = next(self.model.parameters()).device
         batch = {k: v.to(device) for k, v in batch.items()}
         eos_token_id = getattr(self, "eos_token_id", None)

@@ -15,6 +15,7 @@ from .functional import (
     grouped_expert_gemm,
     kv_cache_append,
     moe_route,
+    quantize_kv_e4m3,
     rope_packed_qkv,
     span_attention,
     varlen_attention,

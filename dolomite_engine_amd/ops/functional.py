@@ -694,8 +694,50 @@ def _check_cache(layout: QKVLayout, k_cache, v_cache):
         raise ValueError("k_cache and v_cache must share strides, with a unit stride on the head dim")
 
 
+FP8_KV_DTYPE = torch.float8_e4m3fn
+_E4M3_MAX = 448.0
+
+
+def quantize_kv_e4m3(x):
+    """The fp8 KV cache's quantisation rule (include/dolomite_hip.h) in
+    torch: every (..., D) slice of x gets one fp32 scale, all arithmetic in
+    fp32. Returns (q e4m3 of x's shape, scale fp32 of x's shape without the
+    last dim); x ~ q.float() * scale[..., None]."""
+    xf = x.float()
+    a = xf.abs().amax(dim=-1, keepdim=True).clamp_min(2.0 ** -64)
+    top = torch.full_like(a, _E4M3_MAX)   # tensor / tensor: one IEEE division (scalar / tensor is reciprocal * scalar)
+    q = (xf * (top / a)).to(FP8_KV_DTYPE)
+    return q, (a / top).squeeze(-1)
+
+
+def _check_kv_scales(name, k_cache, k_scale, v_scale):
+    """The scales of an fp8 cache (required), None for a bf16 / fp32 one.
+    True if the cache is fp8."""
+    if k_cache.dtype != FP8_KV_DTYPE:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError(f"{name}: k_scale / v_scale go with a {FP8_KV_DTYPE} cache, got {k_cache.dtype}")
+        return False
+    B, S_cap, Hkv, _ = k_cache.shape
+    for sname, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is None:
+            raise ValueError(f"{name}: an fp8 cache needs k_scale and v_scale")
+        if t.dtype != torch.float32 or t.shape != (B, Hkv, S_cap) or t.device != k_cache.device:
+            raise ValueError(
+                f"{name}: {sname} must be fp32 (B, Hkv, S_cap) = {(B, Hkv, S_cap)} on the cache's device, "
+                f"got {t.dtype} {tuple(t.shape)}"
+            )
+    if k_scale.stride() != v_scale.stride() or k_scale.stride(2) != 1:
+        raise ValueError(f"{name}: k_scale and v_scale must share strides, with a unit stride on the position")
+    return True
+
+
+def _require_bf16_for_fp8(name, qkv):
+    if qkv.dtype != torch.bfloat16:
+        raise TypeError(f"{name}: the fp8 cache kernels take bf16 qkv, got {qkv.dtype}")
+
+
 def kv_cache_append(qkv, layout: QKVLayout, seq_begin, seq_end, k_cache, v_cache, dst_pos,
-                    max_rows: int | None = None):
+                    max_rows: int | None = None, k_scale=None, v_scale=None):
     """Copy the K and V slots of packed (RoPE'd) qkv rows into the cache, in
     place: row seq_begin[b] + i of qkv (T, row_len) goes to cache position
     dst_pos[b] + i of sequence b, for i in [0, seq_end[b] - seq_begin[b]).
@@ -703,18 +745,40 @@ def kv_cache_append(qkv, layout: QKVLayout, seq_begin, seq_end, k_cache, v_cache
     is skipped; nothing else in the cache is touched. seq_begin, seq_end,
     dst_pos: (B,) int32 on qkv's device. max_rows bounds the longest span
     (launch sizing on the GPU; default T). Serves the prefill (the span
-    arrays, dst_pos = 0) and the decode step (one row per sequence)."""
+    arrays, dst_pos = 0) and the decode step (one row per sequence).
+
+    fp8 cache: k_cache / v_cache torch.float8_e4m3fn with k_scale / v_scale
+    fp32 (B, Hkv, S_cap); every appended (position, kv head) slice is
+    quantised by quantize_kv_e4m3's rule and its scale stored. On the GPU qkv
+    must be bf16."""
     lo = layout
     _no_grad_inputs("kv_cache_append", qkv, k_cache, v_cache)
     _check_cache(lo, k_cache, v_cache)
+    fp8 = _check_kv_scales("kv_cache_append", k_cache, k_scale, v_scale)
     B, S_cap = k_cache.shape[:2]
     for name, t in (("seq_begin", seq_begin), ("seq_end", seq_end), ("dst_pos", dst_pos)):
         if t.dtype != torch.int32 or t.shape != (B,):
             raise TypeError(f"{name} must be an int32 tensor of shape ({B},)")
-    if qkv.dim() != 2 or qkv.shape[1] != lo.row_len or qkv.dtype != k_cache.dtype:
+    if qkv.dim() != 2 or qkv.shape[1] != lo.row_len or (not fp8 and qkv.dtype != k_cache.dtype):
         raise ValueError("qkv must be (T, row_len) in the cache dtype")
     T = qkv.shape[0]
     max_rows = T if max_rows is None else min(int(max_rows), T)
+    if qkv.is_cuda and fp8:
+        _require_bf16_for_fp8("kv_cache_append", qkv)
+        qkv = qkv.contiguous()
+        with hip.prof("kv_cache_append_fp8"):
+            hip.check(
+                hip.lib().dolomite_kv_cache_append_fp8(
+                    hip.stream(), hip.ptr(qkv), hip.ptr(seq_begin), hip.ptr(seq_end), hip.ptr(dst_pos),
+                    hip.ptr(k_cache), hip.ptr(v_cache), hip.ptr(k_scale), hip.ptr(v_scale),
+                    B, max_rows, lo.Hkv, lo.D, S_cap,
+                    lo.row_len, lo.k_off, lo.v_off, lo.kv_hstride,
+                    k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+                    k_scale.stride(0), k_scale.stride(1), hip.BF16,
+                ),
+                "kv_cache_append_fp8",
+            )
+        return
     if qkv.is_cuda:
         qkv = qkv.contiguous()
         with hip.prof("kv_cache_append"):
@@ -731,7 +795,14 @@ def kv_cache_append(qkv, layout: QKVLayout, seq_begin, seq_end, k_cache, v_cache
     _, k, v = lo.unpack_cpu(qkv)
     for b, (s, e, p) in enumerate(zip(seq_begin.tolist(), seq_end.tolist(), dst_pos.tolist())):
         n = min(e - s, max_rows, S_cap - p)
-        if n > 0:
+        if n <= 0:
+            continue
+        if fp8:
+            for cache, scales, rows in ((k_cache, k_scale, k), (v_cache, v_scale, v)):
+                q8, sc = quantize_kv_e4m3(rows[s : s + n])    # (n, Hkv, D), (n, Hkv)
+                cache[b, p : p + n] = q8
+                scales[b, :, p : p + n] = sc.t()
+        else:
             k_cache[b, p : p + n] = k[s : s + n]
             v_cache[b, p : p + n] = v[s : s + n]
 
@@ -744,7 +815,7 @@ def decode_num_splits(batch: int, layout: QKVLayout, max_len: int) -> int:
 
 
 def decode_attention(qkv, layout: QKVLayout, k_cache, v_cache, cache_len, scale: float, max_len: int,
-                     num_splits: int | None = None):
+                     num_splits: int | None = None, k_scale=None, v_scale=None):
     """Attention of ONE new token per sequence over its cached keys.
     qkv: (B, row_len) packed rows of the new tokens (only the q slots are
     read; their K/V are already in the cache). k_cache / v_cache:
@@ -759,10 +830,15 @@ def decode_attention(qkv, layout: QKVLayout, k_cache, v_cache, cache_len, scale:
         min(ceil(512 / (B * Hkv * ceil(G / 32))), ceil(ceil(max_len / 64) / 4))
     (at least 1): enough splits for about two workgroups on each of the 256
     CUs, but never less than four 64-key tiles (one per wave) in a split.
-    Inference only: no backward."""
+    Inference only: no backward.
+
+    fp8 cache: k_cache / v_cache torch.float8_e4m3fn with k_scale / v_scale
+    fp32 (B, Hkv, S_cap), as kv_cache_append fills them; the keys and values
+    attended are q8.float() * scale. On the GPU qkv must be bf16."""
     lo = layout
     _no_grad_inputs("decode_attention", qkv, k_cache, v_cache)
     _check_cache(lo, k_cache, v_cache)
+    fp8 = _check_kv_scales("decode_attention", k_cache, k_scale, v_scale)
     B, S_cap = k_cache.shape[:2]
     if qkv.dim() != 2 or qkv.shape != (B, lo.row_len):
         raise ValueError(f"qkv must be (B, row_len) = {(B, lo.row_len)}, got {tuple(qkv.shape)}")
@@ -783,6 +859,23 @@ def decode_attention(qkv, layout: QKVLayout, k_cache, v_cache, cache_len, scale:
         if nsplit > 1:
             n = hip.lib().dolomite_fa_decode_scratch_floats(B, lo.H, lo.D, nsplit)
             scratch = torch.empty(n, dtype=torch.float32, device=qkv.device)
+        if fp8:
+            _require_bf16_for_fp8("decode_attention", qkv)
+            with hip.prof("fa_decode_fp8"):
+                hip.check(
+                    hip.lib().dolomite_fa_decode_fp8(
+                        hip.stream(), hip.ptr(qkv), hip.ptr(k_cache), hip.ptr(v_cache),
+                        hip.ptr(k_scale), hip.ptr(v_scale), hip.ptr(o),
+                        hip.ptr(scratch), hip.ptr(cache_len), B, lo.H, lo.Hkv, lo.D, lo.G, max_len, nsplit,
+                        lo.row_len, lo.q_gstride,
+                        k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+                        v_cache.stride(0), v_cache.stride(1), v_cache.stride(2),
+                        k_scale.stride(0), k_scale.stride(1),
+                        float(scale), hip.BF16,
+                    ),
+                    "fa_decode_fp8",
+                )
+            return o
         with hip.prof("fa_decode"):
             hip.check(
                 hip.lib().dolomite_fa_decode(
@@ -804,8 +897,11 @@ def decode_attention(qkv, layout: QKVLayout, k_cache, v_cache, cache_len, scale:
         n = min(max(n, 0), max_len)
         if n == 0:
             continue
-        kb = k_cache[b, :n].float().repeat_interleave(G, dim=1)  # (n, H, D)
-        vb = v_cache[b, :n].float().repeat_interleave(G, dim=1)
+        kb, vb = k_cache[b, :n].float(), v_cache[b, :n].float()  # (n, Hkv, D)
+        if fp8:
+            kb = kb * k_scale[b, :, :n].t().unsqueeze(-1)
+            vb = vb * v_scale[b, :, :n].t().unsqueeze(-1)
+        kb, vb = kb.repeat_interleave(G, dim=1), vb.repeat_interleave(G, dim=1)  # (n, H, D)
         sc = torch.einsum("hd,nhd->hn", q[b].float(), kb) * scale
         o[b] = torch.einsum("hn,nhd->hd", torch.softmax(sc, dim=-1), vb)
     return o.reshape(B, lo.H * lo.D).to(qkv.dtype)

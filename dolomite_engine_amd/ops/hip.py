@@ -50,6 +50,16 @@ _SIGNATURES = {
          _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
         _i32,
     ),
+    "dolomite_kv_cache_append_fp8": (
+        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32],
+        _i32,
+    ),
+    "dolomite_fa_decode_fp8": (
+        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
+        _i32,
+    ),
     "dolomite_fa_extend_scratch_floats": ([_i32, _i32, _i32, _i32, _i32], _i64),
     "dolomite_fa_extend": (
         [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32,

@@ -299,7 +299,8 @@ int dolomite_fa_dropout_mask_probe(dolomite_stream_t stream, uint8_t* out,
 /* ------------------------------------------------------------------------
  * KV cache and single-token decode attention (inference; the reference's
  * dense flash path with a cache, attention/flash.py:42-43 and the
- * query_length == 1 branch at :94-100). bf16 only.
+ * query_length == 1 branch at :94-100). bf16 here; the e4m3 cache has entry
+ * points of its own below (dolomite_kv_cache_append_fp8 / dolomite_fa_decode_fp8).
  *
  * Cache layout, shared by both entry points (elements):
  *   k_cache[b, s, j, d] = k_cache + b*bstride + s*tstride + j*hstride + d
@@ -375,6 +376,59 @@ int dolomite_fa_decode(dolomite_stream_t stream,
                        int64_t k_bstride, int64_t k_tstride, int64_t k_hstride,
                        int64_t v_bstride, int64_t v_tstride, int64_t v_hstride,
                        float scale, int dtype);
+
+/* ------------------------------------------------------------------------
+ * fp8 KV cache: the cache halves its bytes and a decode step its HBM read.
+ *   k_cache / v_cache: OCP e4m3 bytes (torch.float8_e4m3fn), addressed like
+ *     the bf16 cache with strides in elements (= bytes), unit stride on d.
+ *   k_scale / v_scale: fp32, one per (sequence, kv head, position):
+ *     scale[b, j, s] = scale + b*scale_bstride + j*scale_hstride + s, the
+ *     natural allocation a contiguous (B, Hkv, S_cap) tensor each.
+ * Quantisation rule of one (position, kv head) slice x of D bf16 values, all
+ * arithmetic in fp32 (IEEE division, one rounding per operation):
+ *   a = max(max_d |x[d]|, 2^-64), scale = a / 448, inv = 448 / a,
+ *   q[d] = e4m3 round-to-nearest-even of x[d] * inv;   x[d] ~ q[d] * scale.
+ * An all-zero slice quantises to zeros. NaN / Inf in x: unspecified.
+ *
+ * dolomite_kv_cache_append_fp8: dolomite_kv_cache_append's arguments and
+ * semantics (spans, dst_pos, max_rows — rows at and beyond it are not
+ * appended —, positions outside [0, S_cap) skipped, nothing else written in
+ * the cache or the scales), quantising on the way. qkv is bf16 (`dtype`).
+ * Deterministic. 16-byte loads and 8-byte stores: D and every stride /
+ * offset but the scale strides in units of 8 elements.
+ * Error codes: 9010 dtype != bf16, 9030 negative size, Hkv <= 0,
+ * batch > 65535 or more than 2^31 lane slots per sequence, 9031 D or a
+ * stride not a positive multiple of 8, or D > 128.
+ *
+ * dolomite_fa_decode_fp8: dolomite_fa_decode over such a cache — the same
+ * grid, key split, partials, scratch (dolomite_fa_decode_scratch_floats) and
+ * ascending-order combine; q and o are bf16 (`dtype`). The K scale multiplies
+ * the fp32 score, the V scale the softmax weight before it is packed to bf16;
+ * the row sum is of the unscaled weights. Keys at and beyond cache_len[b]
+ * never influence the result whatever bytes and scales they hold, and
+ * nothing at or beyond position max_len is read, for any capacity.
+ * Error codes: dolomite_fa_decode's, and 9031 also for a cache stride that is
+ * not a multiple of 8.
+ * ---------------------------------------------------------------------- */
+int dolomite_kv_cache_append_fp8(dolomite_stream_t stream, const void* qkv,
+                                 const int32_t* src_begin, const int32_t* src_end,
+                                 const int32_t* dst_pos, void* k_cache, void* v_cache,
+                                 float* k_scale, float* v_scale,
+                                 int batch, int max_rows, int Hkv, int D, int S_cap,
+                                 int64_t row_tstride, int64_t k_off, int64_t v_off, int64_t kv_hstride,
+                                 int64_t cache_bstride, int64_t cache_tstride, int64_t cache_hstride,
+                                 int64_t scale_bstride, int64_t scale_hstride, int dtype);
+int dolomite_fa_decode_fp8(dolomite_stream_t stream,
+                           const void* q, const void* k_cache, const void* v_cache,
+                           const float* k_scale, const float* v_scale, void* o,
+                           float* scratch, const int32_t* cache_len,
+                           int batch, int H, int Hkv, int D, int G,
+                           int max_len, int nsplit,
+                           int64_t q_tstride, int64_t q_gstride,
+                           int64_t k_bstride, int64_t k_tstride, int64_t k_hstride,
+                           int64_t v_bstride, int64_t v_tstride, int64_t v_hstride,
+                           int64_t scale_bstride, int64_t scale_hstride,
+                           float scale, int dtype);
 
 /* dolomite_fa_extend: n_b >= 0 new query tokens per sequence against the
  * cache, causally (a continued conversation, a chunk of a chunked prefill,
