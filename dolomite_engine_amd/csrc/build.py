@@ -16,12 +16,12 @@ PKG = CSRC.parent
 REPO = PKG.parent
 SO_PATH = PKG / "libdolomite_hip.so"
 
-SOURCES = [CSRC / "elementwise.hip", CSRC / "attention.hip", CSRC / "decode.hip", CSRC / "moe_gemm.hip", CSRC / "data_index.cpp", CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip"]
+SOURCES = [CSRC / "elementwise.hip", CSRC / "attention.hip", CSRC / "decode.hip", CSRC / "moe_gemm.hip", CSRC / "data_index.cpp", CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip", CSRC / "extend_fp8.hip"]
 
 # Sources compiled on their own, with packed fp32 VALU ops (v_pk_mul_f32 and
 # kin) off, and linked in as objects. The other sources keep the one-command
 # build they were measured with.
-NO_PACKED_FP32 = [CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip"]
+NO_PACKED_FP32 = [CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip", CSRC / "extend_fp8.hip"]
 _NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 _COMMON = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -31,7 +31,7 @@ def _needs_rebuild() -> bool:
     if not SO_PATH.exists():
         return True
     so_mtime = SO_PATH.stat().st_mtime
-    deps = SOURCES + [CSRC / "common.h", CSRC / "mfma_tiles.h", REPO / "include" / "dolomite_hip.h"]
+    deps = SOURCES + [CSRC / "common.h", CSRC / "mfma_tiles.h", CSRC / "extend_common.h", REPO / "include" / "dolomite_hip.h"]
     return any(p.stat().st_mtime > so_mtime for p in deps)
 
 

@@ -41,24 +41,6 @@
 #define D8_WAVES 4      // waves per workgroup
 #define D8_KTILE 64     // keys per wave step
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// 8 e4m3 bytes in memory order -> bf16x8, exact.
-__device__ __forceinline__ bf16x8 e4m3x8_to_bf16x8(u32x2 w) {
-    bf16x8 r;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const bf16x2 lo = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[h], 1.0f, false);
-        const bf16x2 hi = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[h], 1.0f, true);
-        r[4 * h + 0] = lo[0];
-        r[4 * h + 1] = lo[1];
-        r[4 * h + 2] = hi[0];
-        r[4 * h + 3] = hi[1];
-    }
-    return r;
-}
-
 // load_bf16x8_guard for 8 e4m3 bytes: one 8-byte load from an address clamped
 // into the row, zero bytes (+0) in the pad or for an invalid row.
 __device__ __forceinline__ u32x2 load_e4m3x8_guard(const uint8_t* p, int d0, int D, bool valid) {

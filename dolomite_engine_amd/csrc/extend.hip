@@ -44,31 +44,7 @@
 //
 // Fragment layouts and "permuted key order": see attention.hip.
 
-#include "mfma_tiles.h"
-
-#define EXT_LOG2E 1.44269504088896340736f
-
-#define EXT_COLS 128     // (query, head) columns per workgroup: 8 waves x 16
-#define EXT_KTILE 64     // keys per staged tile
-
-// The new-token span and key count of sequence b, every value clamped so
-// that bad arguments cannot address outside qkv / o / the cache: rows
-// [s0, s0 + n) with 0 <= s0, s0 + n <= T and n <= max_new; len in
-// [0, max_len]; past = len - n, at least 0.
-struct ExtSeq {
-    int s0, n, len, past;
-};
-
-__device__ __forceinline__ ExtSeq ext_seq(const int32_t* seq_begin, const int32_t* seq_end,
-                                          const int32_t* cache_len, int b, int max_new, int max_len, int T) {
-    ExtSeq s;
-    s.s0 = min(max(__builtin_amdgcn_readfirstlane(seq_begin[b]), 0), T);
-    const int e = __builtin_amdgcn_readfirstlane(seq_end[b]);
-    s.n = min(min(max(e - s.s0, 0), max_new), T - s.s0);
-    s.len = min(max(__builtin_amdgcn_readfirstlane(cache_len[b]), 0), max_len);
-    s.past = max(s.len - s.n, 0);
-    return s;
-}
+#include "extend_common.h"
 
 template <int DPAD>
 __global__ void __launch_bounds__(512, 4) fa_extend_kernel(
@@ -331,6 +307,17 @@ __global__ void __launch_bounds__(64) fa_extend_combine_kernel(
     *(bf16x4*)&o[((int64_t)(sq.s0 + i) * H + h) * D + d0] = ov;
 }
 
+// Host side of the combine, shared with extend_fp8.hip (same partials).
+int dol_fa_extend_combine(hipStream_t s, const float* part_o, const float* part_m, const float* part_l,
+                          __bf16* o, const int32_t* seq_begin, const int32_t* seq_end,
+                          const int32_t* cache_len, int64_t rows, int max_new, int max_len, int T, int H,
+                          int D, int nsplit) {
+    hipLaunchKernelGGL(fa_extend_combine_kernel, dim3((unsigned)rows), dim3(64), 0, s,
+                       part_o, part_m, part_l, o, seq_begin, seq_end, cache_len,
+                       max_new, max_len, T, H, D, nsplit);
+    return dol_last_error();
+}
+
 extern "C" int64_t dolomite_fa_extend_scratch_floats(int batch, int max_new, int H, int D, int nsplit) {
     if (batch < 0 || max_new < 0 || H < 0 || D < 0 || nsplit < 1) return -1;
     if (nsplit == 1) return 0;
@@ -356,10 +343,8 @@ static int launch_fa_extend(hipStream_t s, const __bf16* q, const __bf16* kc, co
                        q_ts, q_gs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale);
     int rc = dol_last_error();
     if (rc != 0 || nsplit == 1) return rc;
-    hipLaunchKernelGGL(fa_extend_combine_kernel, dim3((unsigned)nrows), dim3(64), 0, s,
-                       part_o, part_m, part_l, o, seq_begin, seq_end, cache_len,
-                       max_new, max_len, T, H, D, nsplit);
-    return dol_last_error();
+    return dol_fa_extend_combine(s, part_o, part_m, part_l, o, seq_begin, seq_end, cache_len,
+                                 nrows, max_new, max_len, T, H, D, nsplit);
 }
 
 extern "C" int dolomite_fa_extend(dolomite_stream_t stream,

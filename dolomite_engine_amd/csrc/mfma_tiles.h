@@ -137,6 +137,25 @@ __device__ __forceinline__ bf16x8 load_bf16x8_guard(const __bf16* p, int d0, int
     return r;
 }
 
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// 8 e4m3 bytes in memory order -> bf16x8, exact (the fp8 KV cache kernels:
+// decode_fp8.hip, extend_fp8.hip).
+__device__ __forceinline__ bf16x8 e4m3x8_to_bf16x8(u32x2 w) {
+    bf16x8 r;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bf16x2 lo = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[h], 1.0f, false);
+        const bf16x2 hi = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[h], 1.0f, true);
+        r[4 * h + 0] = lo[0];
+        r[4 * h + 1] = lo[1];
+        r[4 * h + 2] = hi[0];
+        r[4 * h + 3] = hi[1];
+    }
+    return r;
+}
+
 // Store a transposed accumulator (head dim 16*dc + 4*lg + x on the
 // registers, the row on l & 15) as bf16: 4 contiguous head-dim elements per
 // lane and block, one 8-byte store. D % 8 == 0 on this path: a 4-wide group

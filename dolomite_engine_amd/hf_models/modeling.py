@@ -272,7 +272,15 @@ class KVCache:
     (B, Hkv, max_length) fp32 (None lists otherwise) — half the bytes held and
     half the bytes a decode step reads. The prefill still attends in bf16 from
     the unquantised K/V; only the append quantises. On the GPU the model must
-    be bf16; the extend step (multi_token) has no fp8 kernel yet."""
+    be bf16.
+
+    The extend step on an fp8 cache: the constructor still refuses
+    multi_token=True with kv_dtype="fp8" (a pinned test holds that refusal
+    until a follow-up lifts it); opt in by setting cache.multi_token = True on
+    the constructed fp8 cache. The append runs before the attention, so an
+    extend step attends the QUANTISED K/V of its own new tokens too, while the
+    one-shot prefill attends unquantised K/V: a chunked and a one-shot prefill
+    of the same prompt differ by the quantisation."""
 
     def __init__(self, config: GPTDolomiteConfig, batch_size: int, max_length: int, dtype, device,
                  multi_token: bool = False, kv_dtype: str | None = None):
@@ -286,7 +294,10 @@ class KVCache:
         self.k_scale = self.v_scale = [None] * config.n_layer
         if kv_dtype == "fp8":
             if self.multi_token:
-                raise NotImplementedError("multi_token=True with an fp8 KV cache: the extend kernel is bf16-only")
+                raise NotImplementedError(
+                    "multi_token=True with kv_dtype='fp8' is not accepted by the constructor yet: to run the "
+                    "extend step on an fp8 cache, set cache.multi_token = True after construction"
+                )
             if torch.device(device).type == "cuda" and dtype != torch.bfloat16:
                 raise TypeError(f"an fp8 KV cache on the GPU needs a bf16 model, got {dtype}")
             dtype = FP8_KV_DTYPE
@@ -426,7 +437,7 @@ class Attention(nn.Module):
                 if kv.extend:
                     attn_output = extend_attention(
                         qkv, self.layout, seq_begin, seq_end, max_seqlen, kv.k, kv.v, kv.cache_len,
-                        self.softmax_scale, kv.max_len,
+                        self.softmax_scale, kv.max_len, k_scale=kv.k_scale, v_scale=kv.v_scale,
                     )
                 else:
                     attn_output = decode_attention(
@@ -915,7 +926,8 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             spans = (seq_begin, seq_end, max_run)
             new_len = cache.lengths + count
             for i, block in enumerate(self.h):
-                kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + max_run, True)
+                kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + max_run, True,
+                              cache.k_scale[i], cache.v_scale[i])
                 hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
             cache.lengths = new_len
             # position id of each sequence's last real token + 1, unchanged for an all-pad row
@@ -1167,8 +1179,10 @@ class GPTDolomiteForCausalLM(GPTDolomitePreTrainedModel):
         for S + max_new_tokens more positions.
         kv_cache_dtype: None keeps K/V in the model dtype; "fp8" allocates
         the cache as KVCache(..., kv_dtype="fp8") (a caller's cache keeps its
-        own kv_dtype; naming another one here is an error). Not with prefill_chunk_size: the
-        extend step has no fp8 kernel (NotImplementedError).
+        own kv_dtype; naming another one here is an error). Not with
+        prefill_chunk_size yet (NotImplementedError, see KVCache): pass an fp8
+        cache with multi_token set after construction as past_key_values to
+        prefill it in chunks through the fp8 extend kernel.
 
         This is a plain loop, deliberately NOT transformers' GenerationMixin:
         the transformers-5 Cache contract is not implemented, KVCache is the

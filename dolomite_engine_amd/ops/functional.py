@@ -919,7 +919,7 @@ def extend_num_splits(batch: int, layout: QKVLayout, max_new: int, max_len: int)
 
 
 def extend_attention(qkv, layout: QKVLayout, seq_begin, seq_end, max_new: int, k_cache, v_cache, cache_len,
-                     scale: float, max_len: int, num_splits: int | None = None):
+                     scale: float, max_len: int, num_splits: int | None = None, k_scale=None, v_scale=None):
     """Causal attention of SEVERAL new tokens per sequence over its cached
     keys: chunked prefill, the next turn of a cached conversation, the verify
     pass over draft tokens. qkv: (T, row_len) packed rows; sequence b's new
@@ -938,12 +938,18 @@ def extend_attention(qkv, layout: QKVLayout, seq_begin, seq_end, max_new: int, k
     (bitwise reproducible). None picks, with
     base = B * Hkv * ceil(max_new * G / 128) workgroups,
         min(ceil(512 / base), ceil(ceil(max_len / 64) / 4))
-    (at least 1), the decode rule. Inference only: no backward."""
+    (at least 1), the decode rule. Inference only: no backward.
+
+    fp8 cache: k_cache / v_cache torch.float8_e4m3fn with k_scale / v_scale
+    fp32 (B, Hkv, S_cap), as kv_cache_append fills them; the keys and values
+    attended are q8.float() * scale — the new tokens' own too, since their
+    append has quantised them. On the GPU qkv must be bf16."""
     lo = layout
     _no_grad_inputs("extend_attention", qkv, k_cache, v_cache)
     _check_cache(lo, k_cache, v_cache)
+    fp8 = _check_kv_scales("extend_attention", k_cache, k_scale, v_scale)
     B, S_cap = k_cache.shape[:2]
-    if qkv.dim() != 2 or qkv.shape[1] != lo.row_len or qkv.dtype != k_cache.dtype:
+    if qkv.dim() != 2 or qkv.shape[1] != lo.row_len or (not fp8 and qkv.dtype != k_cache.dtype):
         raise ValueError("qkv must be (T, row_len) in the cache dtype")
     for name, t in (("seq_begin", seq_begin), ("seq_end", seq_end), ("cache_len", cache_len)):
         if t.dtype != torch.int32 or t.shape != (B,):
@@ -966,6 +972,24 @@ def extend_attention(qkv, layout: QKVLayout, seq_begin, seq_end, max_new: int, k
         if nsplit > 1:
             n = hip.lib().dolomite_fa_extend_scratch_floats(B, max_new, lo.H, lo.D, nsplit)
             scratch = torch.empty(n, dtype=torch.float32, device=qkv.device)
+        if fp8:
+            _require_bf16_for_fp8("extend_attention", qkv)
+            with hip.prof("fa_extend_fp8"):
+                hip.check(
+                    hip.lib().dolomite_fa_extend_fp8(
+                        hip.stream(), hip.ptr(qkv), hip.ptr(k_cache), hip.ptr(v_cache),
+                        hip.ptr(k_scale), hip.ptr(v_scale), hip.ptr(o),
+                        hip.ptr(scratch), hip.ptr(seq_begin), hip.ptr(seq_end), hip.ptr(cache_len),
+                        B, max_new, T, lo.H, lo.Hkv, lo.D, lo.G, max_len, nsplit,
+                        lo.row_len, lo.q_gstride,
+                        k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+                        v_cache.stride(0), v_cache.stride(1), v_cache.stride(2),
+                        k_scale.stride(0), k_scale.stride(1),
+                        float(scale), hip.BF16,
+                    ),
+                    "fa_extend_fp8",
+                )
+            return o
         with hip.prof("fa_extend"):
             hip.check(
                 hip.lib().dolomite_fa_extend(
@@ -990,8 +1014,11 @@ def extend_attention(qkv, layout: QKVLayout, seq_begin, seq_end, max_new: int, k
         past = length - n
         if n <= 0 or past < 0:
             continue
-        kb = k_cache[b, :length].float().repeat_interleave(G, dim=1)  # (length, H, D)
-        vb = v_cache[b, :length].float().repeat_interleave(G, dim=1)
+        kb, vb = k_cache[b, :length].float(), v_cache[b, :length].float()  # (length, Hkv, D)
+        if fp8:
+            kb = kb * k_scale[b, :, :length].t().unsqueeze(-1)
+            vb = vb * v_scale[b, :, :length].t().unsqueeze(-1)
+        kb, vb = kb.repeat_interleave(G, dim=1), vb.repeat_interleave(G, dim=1)  # (length, H, D)
         sc = torch.einsum("ihd,nhd->hin", q[s : s + n].float(), kb) * scale
         seen = torch.arange(length)[None, :] <= past + torch.arange(n)[:, None]
         p = torch.softmax(sc.masked_fill(~seen, float("-inf")), dim=-1)

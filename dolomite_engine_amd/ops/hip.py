@@ -66,6 +66,11 @@ _SIGNATURES = {
          _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
         _i32,
     ),
+    "dolomite_fa_extend_fp8": (
+        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32],
+        _i32,
+    ),
     "dolomite_fa_grad_finalize": ([_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32], _i32),
     "dolomite_ce_fwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),
     "dolomite_ce_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),

@@ -487,6 +487,36 @@ int dolomite_fa_extend(dolomite_stream_t stream,
                        int64_t v_bstride, int64_t v_tstride, int64_t v_hstride,
                        float scale, int dtype);
 
+/* dolomite_fa_extend_fp8: dolomite_fa_extend over the fp8 KV cache above
+ * (e4m3 k_cache / v_cache, fp32 k_scale / v_scale with the strides of
+ * dolomite_fa_decode_fp8) — the same spans, causal mask, clamps, gap rows,
+ * grid, key split, partials, scratch (dolomite_fa_extend_scratch_floats) and
+ * ascending-order combine; qkv and o are bf16 (`dtype`). The keys and values
+ * attended are q8 * scale, the new tokens' own included (the quantising append
+ * has run). A 64-key tile is converted to bf16 once per workgroup on its way
+ * into LDS (exact); the K scale multiplies the fp32 score, the V scale the
+ * softmax weight before it is packed to bf16, the row sum is of the unscaled
+ * weights. Keys at and beyond cache_len[b] never influence the result
+ * whatever bytes and scales they hold, and neither a cache byte nor a scale
+ * at or beyond position max_len is read, for any capacity.
+ * 8-byte cache loads: D and every stride but the scale strides in units of 8
+ * elements.
+ * Error codes, all returned before any launch: dolomite_fa_extend's (9042
+ * also for a negative scale stride), and 9045 k_scale or v_scale NULL.
+ * ---------------------------------------------------------------------- */
+int dolomite_fa_extend_fp8(dolomite_stream_t stream,
+                           const void* qkv, const void* k_cache, const void* v_cache,
+                           const float* k_scale, const float* v_scale, void* o,
+                           float* scratch, const int32_t* seq_begin, const int32_t* seq_end,
+                           const int32_t* cache_len,
+                           int batch, int max_new, int64_t T, int H, int Hkv, int D, int G,
+                           int max_len, int nsplit,
+                           int64_t q_tstride, int64_t q_gstride,
+                           int64_t k_bstride, int64_t k_tstride, int64_t k_hstride,
+                           int64_t v_bstride, int64_t v_tstride, int64_t v_hstride,
+                           int64_t scale_bstride, int64_t scale_hstride,
+                           float scale, int dtype);
+
 /* MFMA fragment-layout self-test: computes C = A(16x32) @ B(32x16) with the
  * compiled fragment mapping; host verifies against a CPU matmul.
  * A/B bf16 row-major contiguous, C fp32 row-major. */
