@@ -10,6 +10,7 @@
 //   CE        : F.cross_entropy at model_wrapper/pretraining.py:125 /
 //               gpt_dolomite/main.py:200
 //   AdamW     : torch.optim.AdamW (optimization/optimizer.py:74)
+//   GLU       : x0 * act(x1) of the gated MLP (modeling_utils/activations/glu.py:26-28)
 //
 // All HBM-bound: the design rules are coalesced wide loads (bf16x8 /
 // float4), fp32 accumulation, one LDS stash per row to avoid re-reads.
@@ -916,6 +917,204 @@ extern "C" int dolomite_scale_inplace(dolomite_stream_t stream, void* buf, int64
         hipLaunchKernelGGL((scale_kernel<T>), grid, block, 0, (hipStream_t)stream, (T*)buf, n, scale);
         return dol_last_error();
     });
+}
+
+// ===========================================================================
+// GLU activation (glu.py:26-28 on the [up ; gate] c_fc layout): one pass
+// forward (y = up * act(gate)) and one backward (dh = [g*act ; g*up*act']),
+// act and act' recomputed from h. The expressions are stated in
+// include/dolomite_hip.h. A pure stream with no reuse: no LDS, no barriers.
+//
+// Work split: the (R, I) output is a flat list of R * nv vectors (nv = I / V,
+// V = 16 bytes of T, or 1). A workgroup pass covers 256 * U consecutive
+// vectors; lane t owns vectors t, t + 256, ... of it, so a wave's accesses
+// are 1 KiB contiguous runs. All U groups' loads (2 per group forward, 3
+// backward) are issued before the first use: the invalid tail groups load
+// vector 0 instead of branching, and only the stores are predicated. Row and
+// column come from one 64-bit division per lane; the advances by 256 and by
+// the grid stride are (rows, vecs) pairs split on the host, one add and one
+// carry each. Flat offsets are int64_t throughout.
+// ===========================================================================
+
+#ifndef DOLOMITE_GLU_GRID_CAP
+#define DOLOMITE_GLU_GRID_CAP 0  // > 0: at most this many workgroups, grid-stride (measured: DESIGN.md §3)
+#endif
+#ifndef DOLOMITE_GLU_NT_DH
+#define DOLOMITE_GLU_NT_DH 1  // non-temporal dh stores; 0: plain stores (measured: DESIGN.md §3)
+#endif
+
+#define GLU_UNROLL 4
+
+template <int ACT>
+__device__ __forceinline__ void glu_act_grad(float x, float& a, float& da) {
+    if constexpr (ACT == DOLOMITE_ACT_SILU) {
+        float s = __builtin_amdgcn_rcpf(1.f + expf(-x));  // exp -> inf gives s = 0
+        a = x * s;
+        da = s * (1.f + x * (1.f - s));
+    } else if constexpr (ACT == DOLOMITE_ACT_GELU_TANH) {
+        const float k0 = 0.7978845608028654f, k1 = 0.044715f;
+        float x2 = x * x;
+        float u = k0 * x * (1.f + k1 * x2);
+        // tanh through e = exp(-2|u|) in (0, 1]: (1 + t) / 2 and 1 - t^2 come out
+        // without the cancellation of 1 - 2 / (exp(2u) + 1) near |t| = 1, which
+        // put 1e-4 on g*up*act' at |g*up| = 64; nothing here can overflow
+        float e = expf(-2.f * fabsf(u));
+        float r = __builtin_amdgcn_rcpf(1.f + e);
+        float c = u < 0.f ? e * r : r;
+        float dt = 4.f * e * r * r;
+        a = x * c;
+        // dt == 0 wherever x2 can have overflowed: select, not 0 * inf
+        da = c + (dt == 0.f ? 0.f : 0.5f * x * dt * k0 * (1.f + 3.f * k1 * x2));
+    } else if constexpr (ACT == DOLOMITE_ACT_GELU) {
+        float c = 0.5f * (1.f + erff(x * 0.7071067811865476f));
+        a = x * c;
+        da = c + x * expf(-0.5f * x * x) * 0.3989422804014327f;
+    } else {
+        a = fmaxf(x, 0.f);
+        da = x > 0.f ? 1.f : 0.f;
+    }
+}
+
+typedef __bf16 glu_bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float glu_f2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t glu_u4_t __attribute__((ext_vector_type(4)));
+
+// One rounding per element; bf16 through the gfx950 pair conversion
+// (v_cvt_pk_bf16_f32, round-to-nearest-even as f32_to_bf16).
+template <typename T, int V, bool NT>
+__device__ __forceinline__ void glu_store(T* p, const float* v) {
+    if constexpr (sizeof(T) == 2 && V == 8) {
+        glu_u4_t w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            glu_f2_t f = {v[2 * e], v[2 * e + 1]};
+            w[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, glu_bf16x2_t));
+        }
+        if (NT)
+            __builtin_nontemporal_store(w, (glu_u4_t*)p);
+        else
+            *(glu_u4_t*)p = w;
+    } else if constexpr (sizeof(T) == 2) {
+        *p = __builtin_bit_cast(uint16_t, (__bf16)v[0]);
+    } else if constexpr (NT) {
+        VecIO<T, V>::store_nt(p, v);
+    } else {
+        VecIO<T, V>::store(p, v);
+    }
+}
+
+// a flat advance of rows * nv + vecs vectors, vecs < nv
+struct GluStep {
+    int64_t rows, vecs;
+};
+
+__device__ __forceinline__ void glu_advance(int64_t& r, int64_t& c, GluStep s, int64_t nv) {
+    r += s.rows;
+    c += s.vecs;
+    if (c >= nv) {
+        c -= nv;
+        ++r;
+    }
+}
+
+template <typename T, int V, int ACT, bool BWD, bool NT>
+__global__ void __launch_bounds__(256) glu_kernel(
+    const T* __restrict__ g, const T* __restrict__ h, int64_t ld_h, T* __restrict__ out,
+    int64_t I, int64_t nv, int64_t total, GluStep lane_step, GluStep grid_step) {
+    constexpr int U = GLU_UNROLL;
+    const int64_t stride = (int64_t)gridDim.x * (256 * U);
+    int64_t base = (int64_t)blockIdx.x * (256 * U) + threadIdx.x;
+    int64_t r = base / nv, c = base % nv;
+    for (; base - threadIdx.x < total; base += stride) {
+        float up[U][V], gate[U][V], gv[BWD ? U : 1][V];
+        int64_t row[U], col[U];
+        bool ok[U];
+        int64_t ru = r, cu = c;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ok[u] = base + u * 256 < total;
+            row[u] = ok[u] ? ru : 0;
+            col[u] = ok[u] ? cu * V : 0;
+            const T* p = h + row[u] * ld_h + col[u];
+            VecIO<T, V>::load_nt(p, up[u]);
+            VecIO<T, V>::load_nt(p + I, gate[u]);
+            if constexpr (BWD) VecIO<T, V>::load_nt(g + row[u] * I + col[u], gv[u]);
+            glu_advance(ru, cu, lane_step, nv);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float o0[V], o1[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                float a, da;
+                glu_act_grad<ACT>(gate[u][e], a, da);
+                if constexpr (BWD) {
+                    o0[e] = gv[u][e] * a;
+                    o1[e] = gv[u][e] * up[u][e] * da;
+                } else {
+                    o0[e] = up[u][e] * a;
+                }
+            }
+            if (ok[u]) {
+                if constexpr (BWD) {
+                    T* q = out + row[u] * (2 * I) + col[u];
+                    glu_store<T, V, NT>(q, o0);
+                    glu_store<T, V, NT>(q + I, o1);
+                } else {
+                    glu_store<T, V, false>(out + row[u] * I + col[u], o0);
+                }
+            }
+        }
+        glu_advance(r, c, grid_step, nv);
+    }
+}
+
+// fn(Int<ACT>{}) for a DOLOMITE_ACT_* code (validated by the caller)
+template <typename Fn>
+static int select_act(int act, Fn fn) {
+    return select_bool(act < DOLOMITE_ACT_GELU, [&](auto low) {
+        return select_bool((act & 1) != 0, [&](auto odd) {
+            return fn(Int<(low ? 0 : 2) + (odd ? 1 : 0)>{});
+        });
+    });
+}
+
+template <bool BWD>
+static int launch_glu(dolomite_stream_t stream, const void* g, const void* h, int64_t ld_h, void* out,
+                      int64_t R, int64_t I, int act, int dtype) {
+    if (act < DOLOMITE_ACT_SILU || act > DOLOMITE_ACT_RELU) return 9060;
+    if (dtype != DOLOMITE_F32 && dtype != DOLOMITE_BF16) return 9061;
+    if (R < 0 || I < 0) return 9062;
+    if (ld_h < 2 * I) return 9063;
+    if (R == 0 || I == 0) return 0;
+    // the gate half, every row and every buffer start on a 16-byte boundary,
+    // or the V = 1 instantiation runs: fold the three conditions into the
+    // extent select_dtype_vec tests
+    bool aligned = (((uintptr_t)g | (uintptr_t)h | (uintptr_t)out) & 15) == 0;
+    return select_dtype_vec(dtype, aligned ? (I | ld_h) : 1, [&](auto t, auto v) {
+        return select_act(act, [&](auto a) {
+            using T = decltype(t);
+            const int64_t nv = I / v, total = R * nv, pass = 256 * GLU_UNROLL;
+            int64_t blocks = (total + pass - 1) / pass;
+            if (DOLOMITE_GLU_GRID_CAP > 0 && blocks > DOLOMITE_GLU_GRID_CAP) blocks = DOLOMITE_GLU_GRID_CAP;
+            const int64_t stride = blocks * pass;
+            GluStep lane_step = {256 / nv, 256 % nv}, grid_step = {stride / nv, stride % nv};
+            hipLaunchKernelGGL((glu_kernel<T, v, a, BWD, BWD && DOLOMITE_GLU_NT_DH>), dim3((uint32_t)blocks),
+                               dim3(256), 0, (hipStream_t)stream, (const T*)g, (const T*)h, ld_h, (T*)out,
+                               I, nv, total, lane_step, grid_step);
+            return dol_last_error();
+        });
+    });
+}
+
+extern "C" int dolomite_glu_fwd(dolomite_stream_t stream, const void* h, int64_t ld_h,
+                                void* y, int64_t R, int64_t I, int act, int dtype) {
+    return launch_glu<false>(stream, nullptr, h, ld_h, y, R, I, act, dtype);
+}
+
+extern "C" int dolomite_glu_bwd(dolomite_stream_t stream, const void* g, const void* h,
+                                int64_t ld_h, void* dh, int64_t R, int64_t I, int act, int dtype) {
+    return launch_glu<true>(stream, g, h, ld_h, dh, R, I, act, dtype);
 }
 
 extern "C" int dolomite_hip_abi_version(void) { return 2; }

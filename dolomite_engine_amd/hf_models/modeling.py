@@ -36,6 +36,7 @@ from ..ops import (
     fused_cross_entropy,
     fused_layernorm,
     fused_rmsnorm,
+    glu_activation,
     kv_cache_append,
     rope_packed_qkv,
     span_attention,
@@ -536,6 +537,7 @@ class MLP(nn.Module):
         hidden_size = config.n_embd
         intermediate = config.n_inner
         self.act, self.is_glu = _activation(config.activation_function)
+        self.act_name = config.activation_function
 
         init_method = config.init_method
         std = config.initializer_range
@@ -553,8 +555,8 @@ class MLP(nn.Module):
     def forward(self, x):
         x = self.c_fc(x)
         if self.is_glu:
-            a, b = x.chunk(2, dim=-1)  # glu.py:26-28: x0 * act(x1)
-            x = a * self.act(b)
+            # glu.py:26-28: x0 * act(x1); one fused HIP launch on the GPU (csrc/elementwise.hip)
+            x = glu_activation(x, self.act_name)
         else:
             x = self.act(x)
         return self.dropout(self.c_proj(x))

@@ -96,6 +96,7 @@ class SparseMoE(nn.Module):
         self.hidden_size = config.n_embd
         self.intermediate_size = config.n_inner
         self.act, self.is_glu = _activation(config.activation_function)
+        self.act_name = config.activation_function
 
         self.gate = ParameterizedLinear(self.hidden_size, config.num_experts, bias=False, std=config.initializer_range)
         std = config.initializer_range
@@ -148,8 +149,7 @@ class SparseMoE(nn.Module):
         expert_inputs = MoERowsGather.apply(hidden_states, batch_index, inv, self.top_k)
         h = self.c_fc(expert_inputs, num_tokens_per_expert)
         if self.is_glu:
-            a, b = h.chunk(2, dim=-1)
-            h = a * self.act(b)
+            h = ops.glu_activation(h, self.act_name)  # the (pairs, 2I) rows through the same fused op
         else:
             h = self.act(h)
         h = self.c_proj(h, num_tokens_per_expert)

@@ -12,6 +12,7 @@ from .functional import (
     fused_cross_entropy,
     fused_layernorm,
     fused_rmsnorm,
+    glu_activation,
     grouped_expert_gemm,
     kv_cache_append,
     moe_route,

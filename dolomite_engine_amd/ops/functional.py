@@ -16,6 +16,7 @@ oracle/model.py.
 from dataclasses import dataclass
 
 import torch
+import torch.nn.functional as F
 
 from . import hip
 
@@ -1377,3 +1378,79 @@ def moe_route(router_logits, top_k):
     if router_logits.shape[0] * top_k >= 2**31:
         return None
     return MoERoute.apply(router_logits.contiguous(), int(top_k))
+
+
+# ---------------------------------------------------------------------------
+# GLU activation (glu.py:26-28 on the fused c_fc layout [up ; gate])
+# ---------------------------------------------------------------------------
+
+_GLU_BASE = {"swiglu": "silu", "geglu": "gelu_tanh", "reglu": "relu"}
+# base name -> (DOLOMITE_ACT_* code, the torch function of the eager chain)
+_GLU_ACTS = {
+    "silu": (0, F.silu),
+    "swish": (0, F.silu),
+    "gelu_tanh": (1, lambda x: F.gelu(x, approximate="tanh")),
+    "gelu_pytorch_tanh": (1, lambda x: F.gelu(x, approximate="tanh")),
+    "gelu": (2, F.gelu),
+    "relu": (3, F.relu),
+}
+
+
+def _glu_act(name: str):
+    base = _GLU_BASE.get(name, name[: -len("_glu")] if name.endswith("_glu") else None)
+    if base not in _GLU_ACTS:
+        raise NotImplementedError(f"activation {name}")
+    return _GLU_ACTS[base]
+
+
+class GLUActivation(torch.autograd.Function):
+    """One launch forward, one backward (csrc/elementwise.hip); saves only h
+    and recomputes act / act' from it."""
+
+    @staticmethod
+    def forward(ctx, h, act):
+        I = h.shape[-1] // 2
+        h2 = h.reshape(-1, 2 * I)  # rows of a wider buffer stay a view: the kernels take the row stride
+        if h2.stride(-1) != 1 or (h2.shape[0] > 1 and h2.stride(0) < 2 * I):
+            h2 = h2.contiguous()
+        y = torch.empty(h.shape[:-1] + (I,), dtype=h.dtype, device=h.device)
+        ld_h = h2.stride(0) if h2.shape[0] > 1 else 2 * I
+        with hip.prof("glu_fwd"):
+            hip.check(
+                hip.lib().dolomite_glu_fwd(hip.stream(), hip.ptr(h2), ld_h, hip.ptr(y), h2.shape[0], I, act, hip.dt(h)),
+                "glu_fwd",
+            )
+        ctx.save_for_backward(h2)
+        ctx.act, ctx.ld_h, ctx.h_shape = act, ld_h, h.shape
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (h2,) = ctx.saved_tensors
+        R, I = h2.shape[0], h2.shape[1] // 2
+        g = g.contiguous()
+        dh = torch.empty(ctx.h_shape, dtype=h2.dtype, device=h2.device)
+        with hip.prof("glu_bwd"):
+            hip.check(
+                hip.lib().dolomite_glu_bwd(
+                    hip.stream(), hip.ptr(g), hip.ptr(h2), ctx.ld_h, hip.ptr(dh), R, I, ctx.act, hip.dt(h2)
+                ),
+                "glu_bwd",
+            )
+        return dh, None
+
+
+def glu_activation(h, name: str):
+    """`a, b = h.chunk(2, -1); a * act(b)` for a GLU activation name (swiglu,
+    geglu, reglu, <base>_glu). CUDA bf16 / fp32 run the fused HIP kernels,
+    any leading shape; CPU tensors and other dtypes keep the torch lines."""
+    code, fn = _glu_act(name)
+    if not h.is_cuda or h.dtype not in (torch.bfloat16, torch.float32):
+        a, b = h.chunk(2, dim=-1)
+        return a * fn(b)
+    if h.shape[-1] % 2 != 0:
+        raise ValueError(f"glu_activation needs an even last dimension, got {h.shape[-1]}")
+    if h.stride(-1) != 1:
+        raise ValueError("glu_activation needs a contiguous last dimension")
+    return GLUActivation.apply(h, code)

@@ -84,6 +84,8 @@ _SIGNATURES = {
     "dolomite_moe_route_scratch_ints": ([_i64, _i32, _i32], _i64),
     "dolomite_moe_route_fwd": ([_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32], _i32),
     "dolomite_moe_route_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32], _i32),
+    "dolomite_glu_fwd": ([_p, _p, _i64, _p, _i64, _i64, _i32, _i32], _i32),
+    "dolomite_glu_bwd": ([_p, _p, _p, _i64, _p, _i64, _i64, _i32, _i32], _i32),
     "dolomite_mfma_probe": ([_p, _p, _p, _p], _i32),
     "dolomite_tr16_probe": ([_p, _p], _i32),
     "dolomite_tr16_bfrag_probe": ([_p, _p, _p, _i32, _i32, _i32, _i32], _i32),

@@ -658,6 +658,51 @@ int dolomite_moe_route_bwd(dolomite_stream_t stream, const void* d_batch_gates,
                            int64_t T, int E, int top_k, int dtype);
 
 /* ------------------------------------------------------------------------
+ * GLU activation, forward / backward — replaces the torch chain
+ * `a, b = h.chunk(2, -1); a * act(b)` of the gated MLP (glu.py:26-28) and its
+ * autograd backward (two multiplies, the activation's backward, a cat) on the
+ * fused c_fc layout [up ; gate] that hf_models/conversion.py writes.
+ *   h : (R, 2I) row-major, row stride ld_h >= 2I elements (a view into a wider
+ *       buffer is fine); up = h[:, :I], gate = h[:, I:2I]
+ *   fwd: y (R, I) dense,   y[r, c]       = up * act(gate)
+ *   bwd: g = dL/dy (R, I) dense, dh (R, 2I) dense (row stride 2I),
+ *                          dh[r, c]      = g * act(gate)
+ *                          dh[r, I + c]  = g * up * act'(gate)
+ * The backward recomputes act and act' from h: nothing but h is saved. Every
+ * element of y / dh is written (no memset needed), evaluated in fp32 from the
+ * loaded values and rounded once to `dtype`. With s(x) = 1 / (1 + exp(-x)),
+ * k0 = sqrt(2/pi), k1 = 0.044715:
+ *   DOLOMITE_ACT_SILU       act = x s(x)          act' = s (1 + x (1 - s))
+ *   DOLOMITE_ACT_GELU_TANH  u = k0 x (1 + k1 x^2), e = exp(-2|u|), r = 1 / (1 + e)
+ *                           c = (1 + tanh u) / 2 = r for u >= 0, e r for u < 0
+ *                           d = 1 - tanh^2 u     = 4 e r^2
+ *                           act = x c             act' = c + x d k0 (1 + 3 k1 x^2) / 2
+ *                           (the second term is +0 where d == 0). tanh as
+ *                           1 - 2 / (exp(2u) + 1) loses 1 + t and 1 - t^2 to
+ *                           cancellation near saturation; this form does not.
+ *   DOLOMITE_ACT_GELU       c = (1 + erf(x / sqrt 2)) / 2
+ *                           act = x c             act' = c + x exp(-x^2 / 2) / sqrt(2 pi)
+ *   DOLOMITE_ACT_RELU       act = max(x, 0)       act' = 1 for x > 0, else 0
+ * s, c and d saturate (to 0 or 1) for finite x of any size: no inf * 0 and
+ * no inf / inf. NaN and Inf inputs are unspecified.
+ * Lanes move 16-byte vectors (8 bf16 / 4 fp32) when I and ld_h are multiples
+ * of that width and h, y, g, dh are 16-byte aligned; any other I >= 1 runs an
+ * element-per-lane instantiation. R == 0 or I == 0 launches nothing.
+ * Error codes, all returned before any launch: 9060 unknown act, 9061 dtype
+ * not fp32 / bf16, 9062 R < 0 or I < 0, 9063 ld_h < 2I.
+ * ---------------------------------------------------------------------- */
+enum dolomite_act {
+    DOLOMITE_ACT_SILU = 0,
+    DOLOMITE_ACT_GELU_TANH = 1,
+    DOLOMITE_ACT_GELU = 2,
+    DOLOMITE_ACT_RELU = 3
+};
+int dolomite_glu_fwd(dolomite_stream_t stream, const void* h, int64_t ld_h,
+                     void* y, int64_t R, int64_t I, int act, int dtype);
+int dolomite_glu_bwd(dolomite_stream_t stream, const void* g, const void* h,
+                     int64_t ld_h, void* dh, int64_t R, int64_t I, int act, int dtype);
+
+/* ------------------------------------------------------------------------
  * Host-side dataset index builders (CPU; the reference's only native
  * component, data/megatron/utils/helpers.cpp).
  * build_sample_idx: pack epoch-replicated documents into seq_length+1 token
