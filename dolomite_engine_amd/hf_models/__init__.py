@@ -19,6 +19,7 @@ from .moe import (
     ParameterizedExperts,
     SparseMoE,
 )
+from .quantization import Fp8Linear, quantize_linears_fp8
 
 
 def register_model_classes() -> None:

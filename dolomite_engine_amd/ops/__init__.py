@@ -9,6 +9,8 @@ from .functional import (
     draw_attention_dropout_seed,
     extend_attention,
     extend_num_splits,
+    fp8_linear,
+    fp8_linear_num_splits,
     fused_cross_entropy,
     fused_layernorm,
     fused_rmsnorm,
@@ -17,6 +19,7 @@ from .functional import (
     kv_cache_append,
     moe_route,
     quantize_kv_e4m3,
+    quantize_weight_e4m3,
     rope_packed_qkv,
     span_attention,
     varlen_attention,

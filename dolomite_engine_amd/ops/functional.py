@@ -711,6 +711,16 @@ def quantize_kv_e4m3(x):
     return q, (a / top).squeeze(-1)
 
 
+def quantize_weight_e4m3(w):
+    """Per-output-channel e4m3 quantisation of a linear's weight (N, K), by
+    quantize_kv_e4m3's rule on every weight row, all arithmetic in fp32:
+    scale[n] = max(amax|w[n, :]|, 2^-64) / 448, wq[n, :] = e4m3(w[n, :] * (448 / amax)).
+    Returns (wq e4m3 (N, K), scale fp32 (N,)); w ~ wq.float() * scale[:, None].
+    Runs once per model, in torch."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_e4m3: weight must be (N, K), got {tuple(w.shape)}")
+    return quantize_kv_e4m3(w)
+
 def _check_kv_scales(name, k_cache, k_scale, v_scale):
     """The scales of an fp8 cache (required), None for a bf16 / fp32 one.
     True if the cache is fp8."""
@@ -1025,6 +1035,80 @@ def extend_attention(qkv, layout: QKVLayout, seq_begin, seq_end, max_new: int, k
         p = torch.softmax(sc.masked_fill(~seen, float("-inf")), dim=-1)
         o[s : s + n] = torch.einsum("hin,nhd->ihd", p, vb)
     return o.reshape(T, lo.H * lo.D).to(qkv.dtype)
+
+
+# ---------------------------------------------------------------------------
+# fp8 (e4m3) weight-only linear (inference only)
+# ---------------------------------------------------------------------------
+
+FP8_LINEAR_MAX_ROWS = 64      # rows the skinny-GEMM kernel serves
+
+
+def fp8_linear_num_splits(M: int, N: int, K: int) -> int:
+    """The split-K count fp8_linear's kernel picks for num_splits=None
+    (dolomite_fp8_linear_num_splits in include/dolomite_hip.h)."""
+    n = hip.lib().dolomite_fp8_linear_num_splits(M, N, K)
+    if n < 1:
+        raise ValueError(f"fp8_linear_num_splits: no kernel for M, N, K = {(M, N, K)}")
+    return n
+
+
+def fp8_linear(x, wq, scale, bias=None, num_splits: int | None = None):
+    """y = x @ (wq * scale[:, None])^T (+ bias): a linear whose weight is
+    stored as e4m3 with one fp32 scale per output channel (W8A16), as
+    quantize_weight_e4m3 makes it. x: (..., K); wq: torch.float8_e4m3fn
+    (N, K), dense; scale: fp32 (N,); bias: (N,) in x's dtype or None. Returns
+    (..., N) in x's dtype. Inference only: no backward.
+
+    Two documented routes, chosen by the arguments alone:
+      - kernel: a CUDA bf16 x with at most 64 rows (the leading dims
+        flattened) and K % 16 == 0 runs the HIP skinny GEMM, which reads the
+        weight as fp8: the decode step and short extend steps. The rows may
+        be a row-strided view (unit last stride). num_splits forces the
+        split-K count (joined in ascending split order, bitwise
+        reproducible); None takes fp8_linear_num_splits.
+      - dequantised: everything else (CPU tensors, fp32 x, more than 64 rows,
+        K % 16 != 0) computes F.linear(x, wq.to(x.dtype) * scale[:, None].to(x.dtype), bias).
+        This is the prefill's route: compute-bound, one temporary copy of the
+        weight in x's dtype per call. It is not a fallback for a missing
+        kernel: on the kernel route a missing library or a kernel error raises."""
+    _no_grad_inputs("fp8_linear", x, scale, bias)
+    if wq.dtype != FP8_KV_DTYPE or wq.dim() != 2:
+        raise TypeError(f"fp8_linear: wq must be {FP8_KV_DTYPE} (N, K), got {wq.dtype} {tuple(wq.shape)}")
+    N, K = wq.shape
+    if x.dim() < 1 or x.shape[-1] != K:
+        raise ValueError(f"fp8_linear: x must be (..., K = {K}), got {tuple(x.shape)}")
+    if scale.dtype != torch.float32 or scale.shape != (N,):
+        raise ValueError(f"fp8_linear: scale must be fp32 ({N},), got {scale.dtype} {tuple(scale.shape)}")
+    if bias is not None and (bias.shape != (N,) or bias.dtype != x.dtype):
+        raise ValueError(f"fp8_linear: bias must be {x.dtype} ({N},), got {bias.dtype} {tuple(bias.shape)}")
+    if num_splits is not None and int(num_splits) < 1:
+        raise ValueError("fp8_linear: num_splits must be >= 1")
+    M = x.numel() // K
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and 1 <= M <= FP8_LINEAR_MAX_ROWS and K % 16 == 0):
+        return F.linear(x, wq.to(x.dtype) * scale[:, None].to(x.dtype), bias)
+    x2 = x.reshape(M, K)
+    if x2.stride(1) != 1 or x2.stride(0) < K or x2.stride(0) % 8 != 0 or x2.data_ptr() % 16 != 0:
+        x2 = x2.contiguous()
+    wq, scale = wq.contiguous(), scale.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    nsplit = hip.lib().dolomite_fp8_linear_num_splits(M, N, K) if num_splits is None else int(num_splits)
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    scratch = None
+    if nsplit > 1:
+        n = hip.lib().dolomite_fp8_linear_scratch_floats(M, N, K, nsplit)
+        if n < 0:
+            raise ValueError(f"fp8_linear: num_splits = {nsplit} out of range for M, N, K = {(M, N, K)}")
+        scratch = torch.empty(n, dtype=torch.float32, device=x.device)
+    with hip.prof("fp8_linear"):
+        hip.check(
+            hip.lib().dolomite_fp8_linear(
+                hip.stream(), hip.ptr(x2), hip.ptr(wq), hip.ptr(scale), hip.ptr(bias), hip.ptr(y),
+                hip.ptr(scratch), M, N, K, x2.stride(0), nsplit, hip.BF16,
+            ),
+            "fp8_linear",
+        )
+    return y.view(*x.shape[:-1], N)
 
 
 # ---------------------------------------------------------------------------

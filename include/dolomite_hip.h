@@ -517,6 +517,52 @@ int dolomite_fa_extend_fp8(dolomite_stream_t stream,
                            int64_t scale_bstride, int64_t scale_hstride,
                            float scale, int dtype);
 
+/* ------------------------------------------------------------------------
+ * fp8 (e4m3) weight-only linear for 1 to 64 rows (W8A16): the skinny GEMM of
+ * a decode or short extend step, which reads half the weight bytes of the
+ * bf16 F.linear it replaces at modeling_utils/linear.py (ParameterizedLinear).
+ *   y[m, n] = bf16( (sum_k x[m, k] * wq[n, k]) * wscale[n] + bias[n] )
+ *   x:      (M, K) bf16, row m at x + m*x_row_stride, unit stride on k
+ *   wq:     (N, K) OCP e4m3 bytes (torch.float8_e4m3fn), dense
+ *   wscale: (N,) fp32, one per output channel. The quantisation rule is the
+ *           fp8 KV cache's above, applied per weight row:
+ *           scale[n] = max(amax|W[n, :]|, 2^-64) / 448
+ *   bias:   (N,) bf16, or NULL
+ *   y:      (M, N) bf16, dense; every element is written
+ * e4m3 -> bf16 is exact, as are the bf16 products inside the MFMA; the sum is
+ * accumulated in fp32 (in an order that depends on nsplit), multiplied by
+ * wscale[n] once, the bias added, and rounded once to bf16. Rows of x at and
+ * beyond M and channels at and beyond N are never read.
+ *
+ * Split-K: the grid is (ceil(N / 64), nsplit). Split c owns
+ * k in [c*kper, min((c+1)*kper, K)), kper = 64 * ceil(ceil(K / 64) / nsplit);
+ * a split without k is legal and contributes zeros. With nsplit > 1 every
+ * workgroup stores its fp32 partials exclusively into scratch[c][m][n] and a
+ * second kernel sums them in ascending split order before the scale and the
+ * bias: no atomics, bitwise reproducible for fixed arguments.
+ *   dolomite_fp8_linear_num_splits: the default split count,
+ *     min(ceil(256 / ceil(N / 64)), ceil(ceil(K / 64) / 4), max(1, K / (8 M)))
+ *     (at least 1), then lowered to drop empty splits: about one workgroup on
+ *     each of the 256 CUs, at least one 256-wide k tile per split, and no more
+ *     partial bytes (written and read back) than weight bytes. -1 for
+ *     arguments dolomite_fp8_linear rejects.
+ *   scratch: dolomite_fp8_linear_scratch_floats(M, N, K, nsplit) =
+ *     nsplit * M * N floats, 16-byte aligned, caller-owned (0 and may be NULL
+ *     for nsplit == 1; the query returns -1 for invalid arguments).
+ * 16-byte loads: x and wq 16-byte aligned, x_row_stride a multiple of 8.
+ * Error codes, all returned before any launch: 9010 dtype != bf16, 9070
+ * M < 1, 9071 M > 64, 9072 K not a positive multiple of 16, 9073 N < 1 or a
+ * size over its limit (N < 2^31, K <= 2^30), 9074 x_row_stride < K or not a
+ * multiple of 8, or a misaligned pointer, 9075 nsplit < 1 or > 65535, 9076
+ * nsplit > 1 without scratch, 9077 a NULL x, wq, wscale or y.
+ * ---------------------------------------------------------------------- */
+int dolomite_fp8_linear_num_splits(int64_t M, int64_t N, int64_t K);
+int64_t dolomite_fp8_linear_scratch_floats(int64_t M, int64_t N, int64_t K, int nsplit);
+int dolomite_fp8_linear(dolomite_stream_t stream, const void* x, const void* wq,
+                        const float* wscale, const void* bias, void* y, float* scratch,
+                        int64_t M, int64_t N, int64_t K, int64_t x_row_stride,
+                        int nsplit, int dtype);
+
 /* MFMA fragment-layout self-test: computes C = A(16x32) @ B(32x16) with the
  * compiled fragment mapping; host verifies against a CPU matmul.
  * A/B bf16 row-major contiguous, C fp32 row-major. */
