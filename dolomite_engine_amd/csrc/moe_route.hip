@@ -393,6 +393,25 @@ extern "C" int dolomite_moe_route_fwd(dolomite_stream_t stream, const void* logi
     return dol_last_error();
 }
 
+// The first launch alone: selected and gates in pair order, for callers that
+// need no expert sort (the decode MLP of moe_decode.hip).
+extern "C" int dolomite_moe_route_topk(dolomite_stream_t stream, const void* logits,
+                                       int32_t* selected, void* gates, int32_t* scratch,
+                                       int64_t T, int E, int top_k, int dtype) {
+    if (int err = route_check(T, E, top_k, dtype)) return err;
+    if (T == 0) return 0;
+    if (scratch == nullptr) return 9053;
+    hipStream_t st = (hipStream_t)stream;
+    const int ntiles = (int)((T + RT_TILE - 1) / RT_TILE);
+    const int W = route_group_width(E);
+    if (dtype == DOLOMITE_BF16) {
+        ROUTE_BY_WIDTH(launch_topk, uint16_t, W, st, ntiles, logits, selected, gates, scratch, T, E, top_k)
+    } else {
+        ROUTE_BY_WIDTH(launch_topk, float, W, st, ntiles, logits, selected, gates, scratch, T, E, top_k)
+    }
+    return dol_last_error();
+}
+
 extern "C" int dolomite_moe_route_bwd(dolomite_stream_t stream, const void* d_batch_gates,
                                       const int32_t* inv, const int32_t* selected,
                                       const void* logits, void* d_logits,

@@ -853,6 +853,11 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             hs = hs * self.m_emb
         return hs
 
+    def _block_dense_cached(self, block, hs, spans, rope_cos_sin, kv):
+        """One block of a cached forward; a model family whose block returns
+        more than the hidden states overrides this."""
+        return block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
+
     def _forward_dense_cached(self, input_ids, attention_mask, position_ids, token_type_ids, cache):
         """Prefill (cache absent or empty; any S, mask left- or right-padded
         or None): today's span path, plus one kv_cache_append per layer.
@@ -890,7 +895,7 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             dst_pos = torch.zeros(B, dtype=torch.int32, device=device)
             for i, block in enumerate(self.h):
                 kv = _LayerKV(cache.k[i], cache.v[i], dst_pos, None, 0, False, cache.k_scale[i], cache.v_scale[i])
-                hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
+                hs = self._block_dense_cached(block, hs, spans, rope_cos_sin, kv)
             count = seq_end - seq_begin
             cache.lengths.copy_(count)
             # position id of each sequence's last real token + 1 (0 for an all-pad row)
@@ -930,7 +935,7 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             for i, block in enumerate(self.h):
                 kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + max_run, True,
                               cache.k_scale[i], cache.v_scale[i])
-                hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
+                hs = self._block_dense_cached(block, hs, spans, rope_cos_sin, kv)
             cache.lengths = new_len
             # position id of each sequence's last real token + 1, unchanged for an all-pad row
             last = (seq_end.long() - 1).clamp_(min=0)
@@ -960,7 +965,7 @@ class GPTDolomiteModel(GPTDolomitePreTrainedModel):
             for i, block in enumerate(self.h):
                 kv = _LayerKV(cache.k[i], cache.v[i], cache.lengths, new_len, past + 1, False,
                               cache.k_scale[i], cache.v_scale[i])
-                hs = block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)
+                hs = self._block_dense_cached(block, hs, spans, rope_cos_sin, kv)
             cache.lengths = new_len
             cache.next_position = position_ids.reshape(-1).long() + 1
             cache._seq_length = past + 1

@@ -117,7 +117,24 @@ class SparseMoE(nn.Module):
         )
         self.dropout = nn.Identity() if config.resid_pdrop == 0 else nn.Dropout(config.resid_pdrop)
 
-    def forward(self, hidden_states: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    def forward_decode(self, hidden_states: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """The same MLP for the few rows of a decode / short extend step
+        (at most ops.MOE_DECODE_MAX_TOKENS, inference only): top-k and gates
+        in pair order, then the fused expert MLP (csrc/moe_decode.hip) — no
+        expert sort, no host readback."""
+        orig_shape = hidden_states.shape
+        hidden_states = hidden_states.reshape(-1, self.hidden_size)
+        router_logits = self.gate(hidden_states)
+        selected, gates = ops.moe_route_topk(router_logits, self.top_k)
+        out = ops.moe_decode_mlp(
+            hidden_states, selected, gates.to(hidden_states.dtype), self.c_fc.weight, self.c_fc.bias,
+            self.c_proj.weight, self.c_proj.bias, self.act_name,
+        )
+        return self.dropout(out.view(orig_shape)), router_logits
+
+    def forward(self, hidden_states: torch.Tensor, decode: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+        if decode:  # the caller's choice (MoEDolomiteBlock under a KV cache), never made here
+            return self.forward_decode(hidden_states)
         orig_shape = hidden_states.shape
         hidden_states = hidden_states.view(-1, self.hidden_size)
         total_q = hidden_states.shape[0]
@@ -183,14 +200,33 @@ class MoEDolomiteBlock(nn.Module):
             moe_out = moe_out * self.m_residual
         return moe_out, s, router_logits
 
-    def forward_dense(self, hidden_states, attention_bias, rope_cos_sin, implementation):
+    # rows up to which a cached forward takes the fused decode MLP (measured:
+    # DESIGN.md §3 "MoE decode"; the op itself serves MOE_DECODE_MAX_TOKENS)
+    decode_max_rows = ops.MOE_DECODE_MAX_TOKENS
+
+    def _takes_decode_mlp(self, y) -> bool:
+        """A cached step's rows go to ops.moe_decode_mlp when it serves them:
+        few enough rows, bf16 on the GPU (any dtype through the CPU lines),
+        and the expert count / dims of the kernel."""
+        mlp = self.mlp
+        return (
+            y.numel() // y.shape[-1] <= self.decode_max_rows
+            and (not y.is_cuda or y.dtype == torch.bfloat16)
+            and mlp.num_experts <= 64 and mlp.top_k <= min(mlp.num_experts, 8)
+            and mlp.hidden_size % 8 == 0 and mlp.intermediate_size % 8 == 0
+        )
+
+    def forward_dense(self, hidden_states, attention_bias, rope_cos_sin, implementation, kv=None):
         y, _ = self.ln_1(hidden_states)
-        attn_out = self.attn.forward_dense(y, attention_bias, rope_cos_sin, implementation)
+        attn_out = self.attn.forward_dense(y, attention_bias, rope_cos_sin, implementation, kv)
         if self.m_residual is not None:
             attn_out = attn_out * self.m_residual
         hidden_states = attn_out + hidden_states
         y, _ = self.ln_2(hidden_states)
-        moe_out, router_logits = self.mlp(y)
+        if kv is not None and self._takes_decode_mlp(y):
+            moe_out, router_logits = self.mlp(y, decode=True)
+        else:
+            moe_out, router_logits = self.mlp(y)
         if self.m_residual is not None:
             moe_out = moe_out * self.m_residual
         return hidden_states + moe_out, router_logits
@@ -206,12 +242,27 @@ class MoEDolomiteModel(GPTDolomiteModel):
         else:
             super()._init_weights(module)
 
+    def _block_dense_cached(self, block, hs, spans, rope_cos_sin, kv):
+        return block.forward_dense(hs, spans, rope_cos_sin, self.attention_implementation, kv)[0]
+
     def forward(self, input_ids=None, past_key_values=None, attention_mask=None, token_type_ids=None,
                 position_ids=None, inputs_embeds=None, use_cache=None, output_hidden_states=None,
                 return_dict=None, cu_seqlens=None, max_seqlen=None, output_router_logits=False):
-        assert past_key_values is None and not use_cache, (
-            "KV cache / generate() is built for GPTDolomite on flash_attention_2 only; MoEDolomite is out of scope"
-        )
+        if past_key_values is not None or use_cache:
+            # the cache runs on the dense flash_attention_2 path (GPTDolomiteModel.forward's
+            # branches); eager / sdpa MoE models keep refusing it
+            assert self.attention_implementation == "flash_attention_2", (
+                "KV cache / generate() is built for GPTDolomite on flash_attention_2 only; MoEDolomite is out of scope"
+            )
+            if output_router_logits:
+                raise ValueError("router logits are not returned under the KV cache: pass output_router_logits=False")
+            out = super().forward(
+                input_ids, past_key_values=past_key_values, attention_mask=attention_mask,
+                token_type_ids=token_type_ids, position_ids=position_ids, inputs_embeds=inputs_embeds,
+                use_cache=use_cache, output_hidden_states=output_hidden_states,
+                cu_seqlens=cu_seqlens, max_seqlen=max_seqlen,
+            )
+            return MoeModelOutputWithPast(last_hidden_state=out.last_hidden_state, past_key_values=out.past_key_values)
         assert inputs_embeds is None and not output_hidden_states
 
         all_router_logits = () if output_router_logits else None
@@ -317,7 +368,9 @@ class MoEDolomiteForCausalLM(GPTDolomiteForCausalLM):
         """Reference moe_dolomite/main.py:50-130: CLM loss + mixtral-style
         load-balancing aux loss scaled by router_aux_loss_coef."""
         if output_router_logits is None:
-            output_router_logits = self.config.output_router_logits
+            # the config's default does not reach a cached forward, which returns no router logits
+            cached = bool(use_cache) or past_key_values is not None
+            output_router_logits = self.config.output_router_logits and not cached
 
         input_ids, position_ids, token_type_ids, labels, cu_seqlens, max_seqlen = self.prepare_inputs_for_model(
             input_ids=input_ids, inputs_embeds=inputs_embeds, position_ids=position_ids,
@@ -327,9 +380,9 @@ class MoEDolomiteForCausalLM(GPTDolomiteForCausalLM):
         )
 
         transformer_outputs = self.transformer(
-            input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids,
-            position_ids=position_ids, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen,
-            output_router_logits=output_router_logits,
+            input_ids, past_key_values=past_key_values, attention_mask=attention_mask,
+            token_type_ids=token_type_ids, position_ids=position_ids, use_cache=use_cache,
+            cu_seqlens=cu_seqlens, max_seqlen=max_seqlen, output_router_logits=output_router_logits,
         )
         hidden_states = transformer_outputs.last_hidden_state
 
@@ -350,5 +403,6 @@ class MoEDolomiteForCausalLM(GPTDolomiteForCausalLM):
 
         return MoeCausalLMOutputWithPast(
             loss=loss, aux_loss=aux_loss, logits=lm_logits,
+            past_key_values=transformer_outputs.past_key_values,
             router_logits=transformer_outputs.router_logits,
         )

@@ -1,6 +1,7 @@
 """Hot-op surface of the MI355X engine (see include/dolomite_hip.h)."""
 
 from .functional import (
+    MOE_DECODE_MAX_TOKENS,
     QKVLayout,
     adamw_step_flat,
     attention_dropout_keep_mask,
@@ -17,7 +18,9 @@ from .functional import (
     glu_activation,
     grouped_expert_gemm,
     kv_cache_append,
+    moe_decode_mlp,
     moe_route,
+    moe_route_topk,
     quantize_kv_e4m3,
     quantize_weight_e4m3,
     rope_packed_qkv,

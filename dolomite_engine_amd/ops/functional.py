@@ -1538,3 +1538,143 @@ def glu_activation(h, name: str):
     if h.stride(-1) != 1:
         raise ValueError("glu_activation needs a contiguous last dimension")
     return GLUActivation.apply(h, code)
+
+
+# ---------------------------------------------------------------------------
+# MoE decode (csrc/moe_decode.hip): the fused expert MLP of a decode or short
+# extend step, and the routing it needs (pair order, no expert sort).
+# Inference only.
+# ---------------------------------------------------------------------------
+
+MOE_DECODE_MAX_TOKENS = 64    # rows the fused expert MLP serves
+
+
+def moe_route_topk(router_logits, top_k):
+    """(selected (T, top_k) int32, gates (T, top_k) in the logits' dtype) as
+    _moe_route_ref states them: descending logits, equal logits to the lowest
+    expert index, gates the fp32 softmax over the selected logits. CUDA bf16 /
+    fp32 logits with E <= 64 and top_k <= min(E, 8) run the first launch of
+    the routing kernels alone (no scan, no scatter); everything else runs the
+    torch lines. No backward."""
+    _no_grad_inputs("moe_route_topk", router_logits)
+    if router_logits.dim() != 2:
+        raise ValueError(f"moe_route_topk: logits must be (T, E), got {tuple(router_logits.shape)}")
+    T, E = router_logits.shape
+    top_k = int(top_k)
+    if not 1 <= top_k <= E:
+        raise ValueError(f"moe_route_topk: top_k = {top_k} outside [1, E = {E}]")
+    if not (router_logits.is_cuda and router_logits.dtype in (torch.bfloat16, torch.float32)
+            and E <= MOE_ROUTE_MAX_EXPERTS and top_k <= MOE_ROUTE_MAX_TOP_K and 0 < T and T * top_k < 2**31):
+        vals, idx = router_logits.sort(dim=-1, descending=True, stable=True)
+        gates = torch.softmax(vals[:, :top_k].float(), dim=-1).to(router_logits.dtype)
+        return idx[:, :top_k].to(torch.int32), gates
+    router_logits = router_logits.contiguous()
+    dev = router_logits.device
+    selected = torch.empty(T, top_k, dtype=torch.int32, device=dev)
+    gates = torch.empty(T, top_k, dtype=router_logits.dtype, device=dev)
+    scratch = torch.empty(hip.lib().dolomite_moe_route_scratch_ints(T, E, top_k), dtype=torch.int32, device=dev)
+    with hip.prof("moe_route_topk"):
+        hip.check(
+            hip.lib().dolomite_moe_route_topk(
+                hip.stream(), hip.ptr(router_logits), hip.ptr(selected), hip.ptr(gates), hip.ptr(scratch),
+                T, E, top_k, hip.dt(router_logits),
+            ),
+            "moe_route_topk",
+        )
+    return selected, gates
+
+
+def _moe_decode_act(activation: str):
+    """(DOLOMITE_ACT_* code, torch function, is_glu) of an activation name:
+    the GLU names of glu_activation and their bases."""
+    if activation.endswith("glu"):
+        return (*_glu_act(activation), True)
+    if activation not in _GLU_ACTS:
+        raise NotImplementedError(f"activation {activation}")
+    return (*_GLU_ACTS[activation], False)
+
+
+def moe_decode_mlp(x, selected, gates, w_fc, b_fc, w_proj, b_proj, activation: str, _waves: int = 0):
+    """The expert MLP of at most MOE_DECODE_MAX_TOKENS routed tokens:
+
+        out[t] = sum_j gates[t, j] * (W_proj[e] @ act(W_fc[e] @ x[t] + b_fc[e]) + b_proj[e]),
+        e = selected[t, j], summed in ascending j
+
+    x (T, H); selected (T, k) int32 expert ids, distinct within a row; gates
+    (T, k) in x's dtype; w_fc (E, F, H) with F = 2I for a GLU activation
+    (`a, b = chunk(2); a * act(b)`, as glu_activation) and F = I for a base
+    one; w_proj (E, H, I); b_fc (E, F) and b_proj (E, H) or None. Returns
+    (T, H) in x's dtype. Inference only: no backward.
+
+    CUDA tensors must be bf16 and run three HIP launches (csrc/moe_decode.hip:
+    fc + activation, proj * gate, combine) with fp32 sums, h and the output
+    each rounded to bf16 once, no host readback, no sort and no atomics: two
+    calls with the same arguments are bitwise equal. The weight of an expert
+    no token selected is not read. CPU tensors run the torch lines of the
+    formula above in x's dtype. _waves forces the kernel's workgroup size
+    (measurements only)."""
+    _no_grad_inputs("moe_decode_mlp", x, gates, w_fc, b_fc, w_proj, b_proj)
+    code, fn, glu = _moe_decode_act(activation)
+    if x.dim() != 2 or selected.dim() != 2 or w_fc.dim() != 3 or w_proj.dim() != 3:
+        raise ValueError("moe_decode_mlp: x (T, H), selected (T, k), w_fc (E, F, H), w_proj (E, H, I)")
+    T, H = x.shape
+    k = selected.shape[1]
+    E, hp, I = w_proj.shape
+    F_ = 2 * I if glu else I
+    if not 1 <= T <= MOE_DECODE_MAX_TOKENS:
+        raise ValueError(f"moe_decode_mlp serves 1 to {MOE_DECODE_MAX_TOKENS} tokens, got {T}")
+    if hp != H or tuple(w_fc.shape) != (E, F_, H):
+        raise ValueError(
+            f"moe_decode_mlp: activation {activation} with w_proj {tuple(w_proj.shape)} needs w_fc "
+            f"{(E, F_, H)}, got {tuple(w_fc.shape)}"
+        )
+    if selected.dtype != torch.int32 or tuple(selected.shape) != (T, k) or tuple(gates.shape) != (T, k):
+        raise ValueError(f"moe_decode_mlp: selected must be int32 and gates {x.dtype}, both (T, k) = {(T, k)}")
+    if not (1 <= E <= MOE_ROUTE_MAX_EXPERTS and 1 <= k <= min(E, MOE_ROUTE_MAX_TOP_K)):
+        raise ValueError(f"moe_decode_mlp: E = {E}, k = {k} outside E <= 64, k <= min(E, 8)")
+    if H % 8 != 0 or I % 8 != 0:
+        raise ValueError(f"moe_decode_mlp: H = {H} and I = {I} must be multiples of 8")
+    for name, t, shape in (("b_fc", b_fc, (E, F_)), ("b_proj", b_proj, (E, H))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"moe_decode_mlp: {name} must be {shape}, got {tuple(t.shape)}")
+    tensors = [t for t in (x, gates, w_fc, b_fc, w_proj, b_proj) if t is not None]
+    if any(t.dtype != x.dtype for t in tensors) or any(t.device != x.device for t in tensors + [selected]):
+        raise ValueError("moe_decode_mlp: x, gates, weights and biases share one dtype, and all tensors one device")
+
+    if not x.is_cuda:
+        out = torch.zeros_like(x)
+        sel = selected.long()
+        for j in range(k):
+            e = sel[:, j]
+            h = torch.bmm(w_fc[e], x.unsqueeze(-1)).squeeze(-1)
+            if b_fc is not None:
+                h = h + b_fc[e]
+            if glu:
+                a, b = h.chunk(2, dim=-1)
+                h = a * fn(b)
+            else:
+                h = fn(h)
+            y = torch.bmm(w_proj[e], h.unsqueeze(-1)).squeeze(-1)
+            if b_proj is not None:
+                y = y + b_proj[e]
+            out = out + gates[:, j : j + 1] * y
+        return out
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"moe_decode_mlp: CUDA tensors must be bf16, got {x.dtype}")
+    x, selected, gates = x.contiguous(), selected.contiguous(), gates.contiguous()
+    w_fc, w_proj = w_fc.contiguous(), w_proj.contiguous()
+    b_fc = None if b_fc is None else b_fc.contiguous()
+    b_proj = None if b_proj is None else b_proj.contiguous()
+    h = torch.empty(T * k, I, dtype=x.dtype, device=x.device)
+    part = torch.empty(T * k, H, dtype=torch.float32, device=x.device)
+    out = torch.empty(T, H, dtype=x.dtype, device=x.device)
+    with hip.prof("moe_decode_mlp"):
+        hip.check(
+            hip.lib().dolomite_moe_decode_mlp(
+                hip.stream(), hip.ptr(x), hip.ptr(selected), hip.ptr(gates), hip.ptr(w_fc), hip.ptr(b_fc),
+                hip.ptr(w_proj), hip.ptr(b_proj), hip.ptr(h), hip.ptr(part), hip.ptr(out),
+                T, E, k, H, I, code, int(glu), int(_waves), hip.BF16,
+            ),
+            "moe_decode_mlp",
+        )
+    return out

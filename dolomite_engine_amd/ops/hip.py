@@ -87,6 +87,11 @@ _SIGNATURES = {
     "dolomite_moe_route_scratch_ints": ([_i64, _i32, _i32], _i64),
     "dolomite_moe_route_fwd": ([_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32], _i32),
     "dolomite_moe_route_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32], _i32),
+    "dolomite_moe_route_topk": ([_p, _p, _p, _p, _p, _i64, _i32, _i32, _i32], _i32),
+    "dolomite_moe_decode_mlp": (
+        [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
+        _i32,
+    ),
     "dolomite_glu_fwd": ([_p, _p, _i64, _p, _i64, _i64, _i32, _i32], _i32),
     "dolomite_glu_bwd": ([_p, _p, _p, _i64, _p, _i64, _i64, _i32, _i32], _i32),
     "dolomite_mfma_probe": ([_p, _p, _p, _p], _i32),

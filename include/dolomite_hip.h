@@ -702,6 +702,50 @@ int dolomite_moe_route_bwd(dolomite_stream_t stream, const void* d_batch_gates,
                            const int32_t* inv, const int32_t* selected,
                            const void* logits, void* d_logits,
                            int64_t T, int E, int top_k, int dtype);
+/* The first launch of dolomite_moe_route_fwd alone: `selected` and `gates`
+ * (T, top_k) in pair order as stated above, no scan and no scatter. scratch
+ * as for the forward (it receives the per-tile expert histogram). Same error
+ * codes. */
+int dolomite_moe_route_topk(dolomite_stream_t stream, const void* logits,
+                            int32_t* selected, void* gates, int32_t* scratch,
+                            int64_t T, int E, int top_k, int dtype);
+
+/* ------------------------------------------------------------------------
+ * Fused expert MLP of a MoE decode / short extend step: 1 <= T <= 64 tokens,
+ * top_k of E experts each — replaces, for those sizes, the gather, the two
+ * grouped GEMMs, the activation, the gate multiply and the combine of
+ * SparseMoE.forward (moe/base.py:129-160), and needs no expert sort.
+ *   out[t] = sum_j gates[t,j] * (W_proj[e] act(W_fc[e] x[t] + b_fc[e]) + b_proj[e]),
+ *   e = selected[t,j], summed in ascending j
+ *   x        (T, H) bf16, dense        selected (T, top_k) int32, ids of a row distinct
+ *   gates    (T, top_k) bf16
+ *   w_fc     (E, F, H) bf16, dense; F = 2I with glu != 0 (rows [0, I) the `a`
+ *            half, [I, 2I) the `b` half: h = a * act(b)), else F = I (h = act(.))
+ *   w_proj   (E, H, I) bf16, dense     b_fc (E, F), b_proj (E, H) bf16, or NULL
+ *   h        (T*top_k, I) bf16 and part (T*top_k, H) fp32: caller-owned
+ *            scratch, need not be cleared
+ *   out      (T, H) bf16; every element is written
+ * act is a DOLOMITE_ACT_* code (expressions: the GLU section below). Sums are
+ * fp32; h is rounded to bf16 once, out once. Three launches (fc + activation,
+ * proj * gate into part, combine), no host readback, no atomics: bitwise
+ * reproducible for fixed arguments. The weight of an expert no row selects is
+ * not read. Ids outside [0, E) select nothing (their rows of part stay
+ * unwritten); nothing outside the buffers is touched.
+ * waves: 0 takes the occupancy rule (workgroups of 4, 2 or 1 waves of 16
+ * channels each: the largest for which ceil(ceil(N / 16) / waves) *
+ * min(E, T*top_k) >= 256, else 1, N the launch's output width); 1, 2 or 4
+ * forces one.
+ * Error codes, all returned before any launch: 9010 dtype != bf16, 9080 T
+ * outside [1, 64], 9081 E outside [1, 64] or top_k outside [1, min(E, 8)],
+ * 9082 H or I not a positive multiple of 8 (or over 2^24), 9083 unknown act,
+ * 9084 waves not 0 / 1 / 2 / 4, 9085 a NULL buffer, 9086 a misaligned one
+ * (16 bytes: x, w_fc, w_proj, h, part; 8: out).
+ * ---------------------------------------------------------------------- */
+int dolomite_moe_decode_mlp(dolomite_stream_t stream, const void* x, const int32_t* selected,
+                            const void* gates, const void* w_fc, const void* b_fc,
+                            const void* w_proj, const void* b_proj, void* h, float* part,
+                            void* out, int T, int E, int top_k, int H, int I, int act, int glu,
+                            int waves, int dtype);
 
 /* ------------------------------------------------------------------------
  * GLU activation, forward / backward — replaces the torch chain
