@@ -16,12 +16,12 @@ PKG = CSRC.parent
 REPO = PKG.parent
 SO_PATH = PKG / "libdolomite_hip.so"
 
-SOURCES = [CSRC / "elementwise.hip", CSRC / "attention.hip", CSRC / "decode.hip", CSRC / "moe_gemm.hip", CSRC / "data_index.cpp", CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip", CSRC / "extend_fp8.hip", CSRC / "fp8_linear.hip", CSRC / "moe_decode.hip"]
+SOURCES = [CSRC / "elementwise.hip", CSRC / "attention.hip", CSRC / "decode.hip", CSRC / "moe_gemm.hip", CSRC / "data_index.cpp", CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip", CSRC / "extend_fp8.hip", CSRC / "fp8_linear.hip", CSRC / "moe_decode.hip", CSRC / "fp8_gemm.hip"]
 
 # Sources compiled on their own, with packed fp32 VALU ops (v_pk_mul_f32 and
 # kin) off, and linked in as objects. The other sources keep the one-command
 # build they were measured with.
-NO_PACKED_FP32 = [CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip", CSRC / "extend_fp8.hip", CSRC / "fp8_linear.hip", CSRC / "moe_decode.hip"]
+NO_PACKED_FP32 = [CSRC / "extend.hip", CSRC / "moe_route.hip", CSRC / "decode_fp8.hip", CSRC / "extend_fp8.hip", CSRC / "fp8_linear.hip", CSRC / "moe_decode.hip", CSRC / "fp8_gemm.hip"]
 _NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 _COMMON = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]

@@ -4,8 +4,10 @@ A decode step streams every linear's whole weight from HBM for a handful of
 rows. quantize_linears_fp8 stores the four linears of each transformer block
 as e4m3 with one fp32 scale per output channel, and ops.fp8_linear reads them
 as such in its HIP skinny-GEMM kernel (csrc/fp8_linear.hip) whenever a call
-has at most 64 rows: the decode steps and short extend steps. Calls with more
-rows (the prefill) take ops.fp8_linear's dequantised route."""
+has at most 64 rows: the decode steps and short extend steps. Calls of up to
+2048 rows (batched decode, chunked prefill) read them as fp8 in its tiled GEMM
+kernel (csrc/fp8_gemm.hip); longer ones (the large prefill) take
+ops.fp8_linear's dequantised route."""
 
 import torch
 import torch.nn as nn

@@ -10,6 +10,7 @@ from .functional import (
     draw_attention_dropout_seed,
     extend_attention,
     extend_num_splits,
+    fp8_gemm_num_splits,
     fp8_linear,
     fp8_linear_num_splits,
     fused_cross_entropy,

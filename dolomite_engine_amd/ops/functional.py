@@ -1042,14 +1042,28 @@ def extend_attention(qkv, layout: QKVLayout, seq_begin, seq_end, max_new: int, k
 # ---------------------------------------------------------------------------
 
 FP8_LINEAR_MAX_ROWS = 64      # rows the skinny-GEMM kernel serves
+# Rows up to which the tiled GEMM kernel serves calls above FP8_LINEAR_MAX_ROWS
+# (None: no bound). The largest M of {128, ..., 4096} up to which the kernel's
+# median time was at most the dequantised route's at all four linears of the 3B
+# config (profiles/fp8_gemm_ab.txt, tools_fp8_gemm_bench.py).
+FP8_GEMM_MAX_ROWS: int | None = 2048
 
 
 def fp8_linear_num_splits(M: int, N: int, K: int) -> int:
-    """The split-K count fp8_linear's kernel picks for num_splits=None
-    (dolomite_fp8_linear_num_splits in include/dolomite_hip.h)."""
+    """The split-K count fp8_linear's skinny kernel (M <= 64) picks for
+    num_splits=None (dolomite_fp8_linear_num_splits in include/dolomite_hip.h)."""
     n = hip.lib().dolomite_fp8_linear_num_splits(M, N, K)
     if n < 1:
         raise ValueError(f"fp8_linear_num_splits: no kernel for M, N, K = {(M, N, K)}")
+    return n
+
+
+def fp8_gemm_num_splits(M: int, N: int, K: int) -> int:
+    """The split-K count fp8_linear's tiled GEMM kernel (M > 64) picks for
+    num_splits=None (dolomite_fp8_gemm_num_splits in include/dolomite_hip.h)."""
+    n = hip.lib().dolomite_fp8_gemm_num_splits(M, N, K)
+    if n < 1:
+        raise ValueError(f"fp8_gemm_num_splits: no kernel for M, N, K = {(M, N, K)}")
     return n
 
 
@@ -1060,18 +1074,26 @@ def fp8_linear(x, wq, scale, bias=None, num_splits: int | None = None):
     (N, K), dense; scale: fp32 (N,); bias: (N,) in x's dtype or None. Returns
     (..., N) in x's dtype. Inference only: no backward.
 
-    Two documented routes, chosen by the arguments alone:
-      - kernel: a CUDA bf16 x with at most 64 rows (the leading dims
-        flattened) and K % 16 == 0 runs the HIP skinny GEMM, which reads the
-        weight as fp8: the decode step and short extend steps. The rows may
-        be a row-strided view (unit last stride). num_splits forces the
-        split-K count (joined in ascending split order, bitwise
-        reproducible); None takes fp8_linear_num_splits.
-      - dequantised: everything else (CPU tensors, fp32 x, more than 64 rows,
-        K % 16 != 0) computes F.linear(x, wq.to(x.dtype) * scale[:, None].to(x.dtype), bias).
-        This is the prefill's route: compute-bound, one temporary copy of the
-        weight in x's dtype per call. It is not a fallback for a missing
-        kernel: on the kernel route a missing library or a kernel error raises."""
+    Three documented routes, chosen by the arguments alone (M = the leading
+    dims flattened):
+      - skinny kernel: a CUDA bf16 x with at most 64 rows and K % 16 == 0 runs
+        the HIP skinny GEMM, which reads the weight as fp8: the decode step
+        and short extend steps.
+      - tiled kernel: the same with more than 64 rows, up to
+        FP8_GEMM_MAX_ROWS (the measured bound; None: any M), runs the HIP
+        tiled GEMM (128 x 128 tiles), which reads the weight as fp8 too and
+        writes no copy of it: batched decode, chunked prefill, draft
+        verification, short prompts.
+        On both kernel routes the rows may be a row-strided view (unit last
+        stride), and num_splits forces the split-K count (joined in ascending
+        split order, bitwise reproducible); None takes fp8_linear_num_splits
+        or fp8_gemm_num_splits.
+      - dequantised: everything else (CPU tensors, fp32 x, K % 16 != 0, more
+        rows than FP8_GEMM_MAX_ROWS) computes
+        F.linear(x, wq.to(x.dtype) * scale[:, None].to(x.dtype), bias), with
+        one temporary copy of the weight in x's dtype per call. It is not a
+        fallback for a missing kernel: on the kernel routes a missing library
+        or a kernel error raises."""
     _no_grad_inputs("fp8_linear", x, scale, bias)
     if wq.dtype != FP8_KV_DTYPE or wq.dim() != 2:
         raise TypeError(f"fp8_linear: wq must be {FP8_KV_DTYPE} (N, K), got {wq.dtype} {tuple(wq.shape)}")
@@ -1085,28 +1107,31 @@ def fp8_linear(x, wq, scale, bias=None, num_splits: int | None = None):
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("fp8_linear: num_splits must be >= 1")
     M = x.numel() // K
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and 1 <= M <= FP8_LINEAR_MAX_ROWS and K % 16 == 0):
+    rows_ok = M >= 1 and (FP8_GEMM_MAX_ROWS is None or M <= max(FP8_GEMM_MAX_ROWS, FP8_LINEAR_MAX_ROWS))
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and rows_ok and K % 16 == 0):
         return F.linear(x, wq.to(x.dtype) * scale[:, None].to(x.dtype), bias)
+    name = "fp8_linear" if M <= FP8_LINEAR_MAX_ROWS else "fp8_gemm"  # both kernels: one argument list
+    lib = hip.lib()
     x2 = x.reshape(M, K)
     if x2.stride(1) != 1 or x2.stride(0) < K or x2.stride(0) % 8 != 0 or x2.data_ptr() % 16 != 0:
         x2 = x2.contiguous()
     wq, scale = wq.contiguous(), scale.contiguous()
     bias = None if bias is None else bias.contiguous()
-    nsplit = hip.lib().dolomite_fp8_linear_num_splits(M, N, K) if num_splits is None else int(num_splits)
+    nsplit = getattr(lib, f"dolomite_{name}_num_splits")(M, N, K) if num_splits is None else int(num_splits)
     y = torch.empty(M, N, dtype=x.dtype, device=x.device)
     scratch = None
     if nsplit > 1:
-        n = hip.lib().dolomite_fp8_linear_scratch_floats(M, N, K, nsplit)
+        n = getattr(lib, f"dolomite_{name}_scratch_floats")(M, N, K, nsplit)
         if n < 0:
             raise ValueError(f"fp8_linear: num_splits = {nsplit} out of range for M, N, K = {(M, N, K)}")
         scratch = torch.empty(n, dtype=torch.float32, device=x.device)
-    with hip.prof("fp8_linear"):
+    with hip.prof(name):
         hip.check(
-            hip.lib().dolomite_fp8_linear(
+            getattr(lib, f"dolomite_{name}")(
                 hip.stream(), hip.ptr(x2), hip.ptr(wq), hip.ptr(scale), hip.ptr(bias), hip.ptr(y),
                 hip.ptr(scratch), M, N, K, x2.stride(0), nsplit, hip.BF16,
             ),
-            "fp8_linear",
+            name,
         )
     return y.view(*x.shape[:-1], N)
 

@@ -74,6 +74,9 @@ _SIGNATURES = {
     "dolomite_fp8_linear_num_splits": ([_i64, _i64, _i64], _i32),
     "dolomite_fp8_linear_scratch_floats": ([_i64, _i64, _i64, _i32], _i64),
     "dolomite_fp8_linear": ([_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i32], _i32),
+    "dolomite_fp8_gemm_num_splits": ([_i64, _i64, _i64], _i32),
+    "dolomite_fp8_gemm_scratch_floats": ([_i64, _i64, _i64, _i32], _i64),
+    "dolomite_fp8_gemm": ([_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i32], _i32),
     "dolomite_fa_grad_finalize": ([_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32], _i32),
     "dolomite_ce_fwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),
     "dolomite_ce_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32], _i32),

@@ -563,6 +563,47 @@ int dolomite_fp8_linear(dolomite_stream_t stream, const void* x, const void* wq,
                         int64_t M, int64_t N, int64_t K, int64_t x_row_stride,
                         int nsplit, int dtype);
 
+/* ------------------------------------------------------------------------
+ * fp8 (e4m3) weight-only linear for any number of rows (W8A16): the tiled
+ * GEMM that serves ops.fp8_linear above the 64 rows of dolomite_fp8_linear
+ * (batched decode, chunked prefill, draft verification, short prompts). Same
+ * operands, same arithmetic and same argument conventions as
+ * dolomite_fp8_linear above: y[m, n] = bf16( (sum_k x[m, k] * wq[n, k]) *
+ * wscale[n] + bias[n] ), exact e4m3 -> bf16 conversion and products, fp32
+ * accumulation in an order that depends on nsplit, one rounding. The weight
+ * is read as fp8 only; no bf16 copy of it is written anywhere.
+ *
+ * The grid is (ceil(N / 128), ceil(M / 128), nsplit): a workgroup owns a
+ * 128-row x 128-channel tile of y. Split c owns
+ * k in [c*kper, min((c+1)*kper, K)), kper = 128 * ceil(ceil(K / 128) / nsplit);
+ * a split without k is legal and contributes zeros. With nsplit > 1 every
+ * workgroup stores its fp32 partials exclusively into scratch[c][m][n] and a
+ * second kernel sums them in ascending split order before the scale and the
+ * bias: no atomics, bitwise reproducible for fixed arguments.
+ *   dolomite_fp8_gemm_num_splits: the default split count,
+ *     min(ceil(256 / tiles), max(1, floor(ceil(K / 128) / 2)), max(1, K / (4 M)))
+ *     with tiles = ceil(N / 128) * ceil(M / 128), then lowered to drop empty
+ *     splits: about one workgroup on each of the 256 CUs, two k tiles per
+ *     split at least, and partial traffic of at most twice the weight bytes.
+ *     -1 for arguments dolomite_fp8_gemm rejects.
+ *   scratch: dolomite_fp8_gemm_scratch_floats(M, N, K, nsplit) =
+ *     nsplit * M * N floats, 16-byte aligned, caller-owned (0 and may be NULL
+ *     for nsplit == 1; the query returns -1 for invalid arguments).
+ * 16-byte loads: x and wq 16-byte aligned, x_row_stride a multiple of 8.
+ * Error codes, all returned before any launch: 9010 dtype != bf16, 9080
+ * M < 1, 9081 M > 65535 * 128, 9082 K not a positive multiple of 16, 9083
+ * N < 1 or a size over its limit (N < 2^31, K <= 2^30, M * N <= 2^38), 9084
+ * x_row_stride < K or not a multiple of 8, or a misaligned pointer, 9085
+ * nsplit < 1 or > 65535, 9086 nsplit > 1 without scratch, 9087 a NULL x, wq,
+ * wscale or y.
+ * ---------------------------------------------------------------------- */
+int dolomite_fp8_gemm_num_splits(int64_t M, int64_t N, int64_t K);
+int64_t dolomite_fp8_gemm_scratch_floats(int64_t M, int64_t N, int64_t K, int nsplit);
+int dolomite_fp8_gemm(dolomite_stream_t stream, const void* x, const void* wq,
+                      const float* wscale, const void* bias, void* y, float* scratch,
+                      int64_t M, int64_t N, int64_t K, int64_t x_row_stride,
+                      int nsplit, int dtype);
+
 /* MFMA fragment-layout self-test: computes C = A(16x32) @ B(32x16) with the
  * compiled fragment mapping; host verifies against a CPU matmul.
  * A/B bf16 row-major contiguous, C fp32 row-major. */
